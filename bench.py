@@ -1,7 +1,7 @@
 """Headline benchmark: rays/s of one train step (forward + backward of render_rays, both networks,
 64 coarse + 128 fine samples per ray) on N GPUs of one node -- BASELINE.json's metric/config.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--rays 4096] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--rays 4096] [--full [--no-cpu]] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One process per GPU; every rank renders its own 4096 synthetic rays (weak scaling).  The workload is the same at every N
@@ -11,9 +11,16 @@ carries networks AND camera parameters), 3 = configs[3] (the same + the projecte
 every step, NeRF/run_nerf.py:508-598), 4 = configs[4] (NeRF++: two cascade levels, foreground + background networks,
 nerfplusplus/ddp_train_nerf.py:491-550).  At N > 1 ONE all-reduce per step (RCCL) sums the flat fp32 gradient buffer; at
 N = 1 there is no collective.  Rank 0 prints ONE compact JSON
-line (< 4 KB: the contract's keys, `roofline`, `cpu_baseline`, the all-fp32-MFMA step; tests/test_bench_line.py) and writes
-the full record -- per-kernel tables, and at N = 1 short timings of the other configurations (camera curriculum states, PRD
-loss, full-image inference, NeRF++) -- to profiles/bench_detail_n<N>.json, named in the line.  `--gpus N` without a launcher
+line (< 4 KB: the contract's keys, `roofline`, `cpu_baseline`, the all-fp32-MFMA step; tests/test_bench_line.py).
+
+A plain run does what the headline needs and no more: set-up, `--warmup W` steps, `--steps K` timed steps (`ms_per_step` =
+their wall time / K), the line.  `--full` adds everything else -- the events-off rerun, clock / power telemetry, the
+rocprofv3 counter passes, the CPU baseline, at N = 1 short timings of the other configurations (camera curriculum states,
+PRD loss, full-image inference, NeRF++, the all-fp32-MFMA step), at N > 1 the collective on its own -- and writes the full
+record (per-kernel tables included) to profiles/bench_detail_n<N>.json, named in the line (a plain run writes it only to
+a file `--detail` names).  Every run seeds torch's generator (SEED): the same arguments give the same inputs, and
+`--dump-outputs DIR` writes what the last timed step computed (its outputs and the flat gradient buffer) as DIR/<name>.npy,
+so that two builds can be compared output for output.  `--gpus N` without a launcher
 starts its own N ranks.  `roofline` is measured live with HIP events around the dominant kernel's launches on the stream they
 run on, its `traffic` comes from the newest PMC summary whose source hash matches the kernels (tools/round_evidence.sh);
 `cpu_baseline` times the UNMODIFIED reference render_rays at 4096 rays x (64 + 128) on the host cores where its tree is
@@ -37,6 +44,8 @@ PEAK_F32_MFMA_TFLOPS = 157.3              # MI355X_MICROARCH.md "Peak FP32 (matr
 PEAK_16BIT_MFMA_TFLOPS = 2500.0           # ibid., dense bf16 / fp16
 PEAK_HBM_GBS = 8000.0                     # ibid., HBM3E spec (6290 measured with a float4 copy)
 MEASURED_HBM_GBS = 6290.0
+SEED = 0                                  # torch.manual_seed of every run: the same arguments give the same inputs
+DUMP_LIMIT = 64 << 20                     # bytes: what --dump-outputs writes at most, in all
 
 
 def csrc_sha16():
@@ -114,6 +123,30 @@ def floors(name, avg_ms, wgrad_products=3):
             "bound": "mfma" if t_mfma >= t_hbm else "hbm", "frac_mfma": t_mfma / t, "frac_hbm": t_hbm / t,
             "frac": max(t_mfma, t_hbm) / t,
             "tflops": md["flop"] / t / 1e12, "gbytes_per_s": md["bytes"] / t / 1e9}
+
+
+def write_outputs(directory, arrays, limit=DUMP_LIMIT):
+    """--dump-outputs: every tensor of `arrays` as <directory>/<name>.npy -- float64 where it is float64, else float32.
+    Should they come to more than `limit` bytes, each array keeps a share of the budget proportional to its size: a fixed
+    (seeded) sample of its elements, flattened, in index order, so that two builds write the same elements.  -> names"""
+    import re
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        if torch.is_tensor(t):
+            t = t.detach()
+            host[re.sub(r"[^A-Za-z0-9_.-]", "_", name)] = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+    total = sum(x.nbytes for x in host.values())
+    budget = limit - 1024 * len(host)                          # (room for the .npy headers)
+    os.makedirs(directory, exist_ok=True)
+    for name, x in sorted(host.items()):
+        if total > budget:
+            keep = max(1, x.size * budget // total)
+            if keep < x.size:
+                idx = np.sort(np.random.default_rng(SEED).choice(x.size, keep, replace=False))
+                x = x.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), x)
+    return sorted(host)
 
 
 def _time_steps(step, iters):
@@ -451,6 +484,7 @@ def fixed_camera_step(w, reducer):
         g0 = (ret["rgb0"].detach() - w["target"]) * (2 * inv)
         torch.autograd.backward([ret["rgb_map"], ret["rgb0"]], [g1, g0])
         reducer.all_reduce()
+        return ret
     return step
 
 
@@ -477,8 +511,9 @@ def learnable_camera_step(w, reducer, prd=False, prd_sync=False):
         reducer.zero()
         rays_o, rays_d = get_rays_kps_use_camera(H=IMG_H, W=IMG_W, camera_model=w["cam"],
                                                  idx_in_camera_param=w["idx"], kps_list=w["kps"])
-        rgb, _, _, extras = render(H=IMG_H, W=IMG_W, chunk=1 << 15, rays=torch.stack([rays_o, rays_d]), retraw=True,
-                                   camera_model=w["cam"], mode="train", **kw)
+        rgb, disp, acc, extras = render(H=IMG_H, W=IMG_W, chunk=1 << 15, rays=torch.stack([rays_o, rays_d]), retraw=True,
+                                        camera_model=w["cam"], mode="train", **kw)
+        ret = dict(extras, rgb_map=rgb, disp_map=disp, acc_map=acc)
         g1 = (rgb.detach() - w["target"]) * (2 * inv)
         g0 = (extras["rgb0"].detach() - w["target"]) * (2 * inv)
         outs, grads = [rgb, extras["rgb0"]], [g1, g0]
@@ -494,8 +529,10 @@ def learnable_camera_step(w, reducer, prd=False, prd_sync=False):
                                                 camera_model=w["cam"], method="NeRF", i_map=i_map, _sync=prd_sync)
             outs.append(loss)
             grads.append(one * PRD_WEIGHT)
+            ret["prd_loss"] = loss
         torch.autograd.backward(outs, grads)
         reducer.all_reduce()
+        return ret
     return step
 
 
@@ -915,6 +952,13 @@ def main():
     ap.add_argument("--strong", action="store_true",
                     help="strong scaling: --rays is the TOTAL batch, split evenly over the ranks (SURVEY section 8d, C4's second "
                          "figure); default: weak scaling, --rays per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the events-off rerun, clock / power telemetry, the rocprofv3 "
+                         "counter passes, the CPU baseline, the other configurations and arithmetics (N = 1), the collective "
+                         "on its own (N > 1); a plain run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: what the timed path computed in its last step (the step's outputs and the "
+                         "flat gradient buffer) as DIR/<name>.npy, float32, at most 64 MB in all (a fixed sample beyond that)")
     ap.add_argument("--init-timeout", type=float, default=float(os.environ.get("SCNERF_BENCH_INIT_TIMEOUT", "180")),
                     help="N > 1: seconds the rendezvous + communicator start-up, and then the first collective, may take before "
                          "rank 0 prints an error line and every rank exits non-zero")
@@ -952,6 +996,11 @@ def run(a, json_out, guard, rank, world, scale):
         torch.cuda.set_device(local_rank)
         dev = torch.device("cuda", local_rank)
     guard.stage = "build the workload"
+    if a.steps < 1:
+        guard.fail("arguments", "--steps must be at least 1", code=2)
+    # the per-step draws (ops.next_random_call) come from torch's default generator: a fixed seed makes every input of
+    # the timed steps the same from run to run
+    torch.manual_seed(SEED)
 
     from scnerf_amd import ops
     from scnerf_amd.parallel import FlatGradAllReduce
@@ -975,8 +1024,9 @@ def run(a, json_out, guard, rank, world, scale):
 
         def step():
             reducer.zero()
-            npp_step(zero=False)
+            loss = npp_step(zero=False)
             reducer.all_reduce()
+            return {"loss": loss}
     else:
         w = build_world(dev, rank, n)
         if cfg == 1:
@@ -996,14 +1046,14 @@ def run(a, json_out, guard, rank, world, scale):
         for _ in range(a.warmup):
             step()
         sync()
-    live = Telemetry(dev) if (rank == 0 and a.telemetry_seconds > 0) else None
+    live = Telemetry(dev) if (a.full and rank == 0 and a.telemetry_seconds > 0) else None
     with guard.deadline("timed steps", (60 + 2 * a.steps) * scale):
         ops.PROFILE.reset(enabled=True)
         if live:
             live.start()
         t0 = time.perf_counter()
         for _ in range(a.steps):
-            step()
+            last = step()
         sync()
         dt = time.perf_counter() - t0
         in_loop = live.stop() if live else None
@@ -1018,22 +1068,28 @@ def run(a, json_out, guard, rank, world, scale):
         tt = torch.tensor([dt], device=small, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if a.dump_outputs and rank == 0:
+        guard.stage = "writing the last step's outputs"
+        write_outputs(a.dump_outputs, dict(last, grad_flat=reducer.flat))
+    if world > 1 and a.full:
         with guard.deadline("the collective on its own", 120 * scale):
             allreduce_info = rccl_allreduce_probe(dev, int(reducer.flat.numel()))       # the step's collective on its own
     ms = dt / a.steps * 1e3
     guard.stage = "after the timed region"
 
-    # the same K steps without the event pairs (outside the reported figure)
-    sync()
-    t0 = time.perf_counter()
-    for _ in range(a.steps):
-        step()
-    sync()
-    ms_off = (time.perf_counter() - t0) / a.steps * 1e3
+    ms_off = None
+    if a.full:
+        # the same K steps without the event pairs (outside the reported figure)
+        sync()
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            step()
+        sync()
+        ms_off = (time.perf_counter() - t0) / a.steps * 1e3
     # clock / power: the samples taken during the timed steps when there are enough of them (>= 4: ~40 ms of steps), else
     # a loop of its own after the timed region (labelled as such)
     telemetry = None
-    if rank == 0 and world == 1 and a.telemetry_seconds > 0:
+    if a.full and rank == 0 and world == 1 and a.telemetry_seconds > 0:
         # socket power: amdgpu's power1_input is a moving average over about a second -- 0.24 s of timed steps only see it
         # ramp --, so it is read over a loop of its own; the shader clock responds at once and is the timed steps' own
         telemetry = Telemetry(dev).sample_while(step, a.telemetry_seconds)
@@ -1083,8 +1139,8 @@ def run(a, json_out, guard, rank, world, scale):
             P_dom = int(_re.search(r"/P=(\d+)", dom).group(1))
             roof["survey_algorithmic_bytes_per_launch"] = (4 * pd + 16) * P_dom
             rec, path, stale = latest_pmc_traffic()
-            live, live_note = (None, "not requested")
-            if world == 1 and cfg == 1 and not a.no_pmc:
+            live, live_note = (None, "not requested" if a.full else "not measured in a plain run (--full)")
+            if a.full and world == 1 and cfg == 1 and not a.no_pmc:
                 guard.stage = "rocprofv3 counter passes (HBM traffic of this run)"
                 try:
                     live, live_note = live_pmc_traffic(dom, n)
@@ -1144,7 +1200,6 @@ def run(a, json_out, guard, rank, world, scale):
         out = {
             "metric": metric_for(cfg), "value": n * world / (ms * 1e-3),
             "unit": "rays/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": ms,
-            "ms_per_step_events_off": ms_off,
             "higher_is_better": True, "scaling": "strong" if a.strong else "weak", "vs_baseline": None,
             "dtype": {"resident": "f32 (3 x fp16 MFMA products per product, fp32 accumulate)", "fp32": "f32 (fp32 MFMA)"}[ops.mlp_arithmetic()],
             "arithmetic": {
@@ -1179,11 +1234,14 @@ def run(a, json_out, guard, rank, world, scale):
             "step_flop_algorithmic": step_flop,
             "step_tflops": step_flop / (ms * 1e-3) / 1e12,
         }
+        if ms_off is not None:
+            out["ms_per_step_events_off"] = ms_off
         if per_rank_ms is not None:
             out["per_rank_ms_per_step"] = per_rank_ms
-            out["all_reduce_alone"] = allreduce_info
+            if allreduce_info is not None:
+                out["all_reduce_alone"] = allreduce_info
             out["ranks"] = ranks_info
-        if world == 1 and not a.no_extras and cfg == 1:
+        if a.full and world == 1 and not a.no_extras and cfg == 1:
             guard.stage = "extras (other configurations, inference, PSNR)"
             out["extras"] = extras_single_gpu(w, dev, sync)
             # SURVEY section 8(d)'s secondary metric: forward-only rays/s of full-image inference (render_path, 378 x 504,
@@ -1194,18 +1252,20 @@ def run(a, json_out, guard, rank, world, scale):
             if a.backend == "nccl":
                 out["extras"]["rccl_allreduce_single_rank"] = rccl_allreduce_probe(dev, 1202945)
         # the CPU leg IS configs[1]'s render_rays: only the headline configuration is compared with it
-        if world == 1 and not a.no_cpu and cfg == 1:
+        if a.full and world == 1 and not a.no_cpu and cfg == 1:
             guard.stage = "cpu_baseline"
             out["cpu_baseline"] = cpu_baseline(a.cpu_rays)
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
-        # the full record goes to a file; stdout carries the compact line only (a 26 KB line once outgrew the driver's tail)
-        detail = a.detail or os.path.join("profiles", "bench_detail_n%d.json" % world)
-        try:
-            os.makedirs(os.path.dirname(os.path.join(ROOT, detail)) or ".", exist_ok=True)
-            with open(os.path.join(ROOT, detail), "w") as fh:
-                json.dump(out, fh, indent=1)
-        except OSError as e:
-            detail = "not written: %r" % (e,)
+        # the full record goes to a file; stdout carries the compact line only (a 26 KB line once outgrew the driver's tail);
+        # a plain run writes it only where --detail names a file
+        detail = a.detail or (os.path.join("profiles", "bench_detail_n%d.json" % world) if a.full else None)
+        if detail:
+            try:
+                os.makedirs(os.path.dirname(os.path.join(ROOT, detail)) or ".", exist_ok=True)
+                with open(os.path.join(ROOT, detail), "w") as fh:
+                    json.dump(out, fh, indent=1)
+            except OSError as e:
+                detail = "not written: %r" % (e,)
         with guard._lock:
             guard.done = True                       # (from here on a SIGTERM must not add a second line)
             json_out.write(compact_record(out, detail) + "\n")

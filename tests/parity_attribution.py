@@ -16,11 +16,11 @@ import os
 import numpy as np
 import torch
 
-# everything the parity tests measured; tests/conftest.py writes it at the end of the session to
-# gpurun_out/parity_r06.json (travels back from the GPU box; the copy committed under profiles/ is this file)
-# and to profiles/ in the tree the tests ran in
+# everything the parity tests measured; tests/conftest.py writes it at the end of the session, merged over the committed
+# report, to $SCNERF_PARITY_REPORT or else profiles/parity_latest.json (git-ignored: a test run leaves the tree as it was)
 REPORT = {}
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+COMMITTED_REPORT = os.path.join(ROOT, "profiles", "parity_r06.json")
 
 
 def write_report():
@@ -29,18 +29,18 @@ def write_report():
         return
     merged = {}
     try:
-        with open(os.path.join(ROOT, "profiles", "parity_r06.json")) as f:
+        with open(COMMITTED_REPORT) as f:
             merged = json.load(f)
     except (OSError, ValueError):
         pass
     merged.update(REPORT)
-    for d in ("gpurun_out", "profiles"):
-        try:
-            os.makedirs(os.path.join(ROOT, d), exist_ok=True)
-            with open(os.path.join(ROOT, d, "parity_r06.json"), "w") as f:
-                json.dump(merged, f, indent=1, sort_keys=True)
-        except OSError:
-            pass
+    path = os.environ.get("SCNERF_PARITY_REPORT") or os.path.join(ROOT, "profiles", "parity_latest.json")
+    try:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            json.dump(merged, f, indent=1, sort_keys=True)
+    except OSError:
+        pass
 
 
 def _gather(t, idx):

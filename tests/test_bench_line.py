@@ -114,7 +114,7 @@ def test_gpu_bench_runs_the_named_configs_on_two_ranks(tmp_path, config, floats)
     collective on its own are there, and the flat gradient buffer has the size the configuration implies."""
     detail = str(tmp_path / "detail.json")
     line = _run_bench(["--gpus", "2", "--config", str(config), "--backend", "gloo", "--one-device", "--steps", "2", "--warmup", "1",
-                       "--no-cpu", "--rays", "256", "--detail", detail])
+                       "--full", "--no-cpu", "--rays", "256", "--detail", detail])
     assert line["n_gpus"] == 2 and line["config"]["baseline_config"] == config
     assert line["config"]["workload"].startswith("configs[%d]" % config)
     assert "all-reduce/step" in line["config"]["parallelism"]
@@ -132,7 +132,7 @@ def test_gpu_bench_runs_the_named_configs_on_two_ranks(tmp_path, config, floats)
 
 @pytest.mark.gpu
 def test_gpu_bench_says_no_collective_on_one_rank(tmp_path):
-    line = _run_bench(["--steps", "2", "--warmup", "1", "--no-cpu", "--no-extras", "--rays", "256", "--config", "3",
+    line = _run_bench(["--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--no-extras", "--rays", "256", "--config", "3",
                        "--telemetry-seconds", "0.3", "--detail", str(tmp_path / "d.json")])
     assert "no collective at N = 1" in line["config"]["parallelism"] and line["config"]["baseline_config"] == 3
     roof = line["roofline"]
@@ -151,13 +151,35 @@ def test_gpu_bench_single_line(tmp_path):
 
 
 @pytest.mark.gpu
+def test_gpu_plain_run_is_lean_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain run times exactly --steps steps and measures nothing beside them (no CPU baseline, no events-off rerun, no
+    detail file unless --detail names one); two runs with the same arguments dump the same last-step outputs."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("out%d" % k)
+        line = _run_bench(["--steps", "3", "--warmup", "1", "--rays", "256", "--dump-outputs", str(d)])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["cpu_baseline"] is None and "ms_per_step_events_off" not in line and line["detail"] is None
+        dumps.append({f.name: np.load(f) for f in sorted(d.iterdir())})
+    a, b = dumps
+    assert {"rgb_map.npy", "rgb0.npy", "raw.npy", "grad_flat.npy"} <= set(a) and set(a) == set(b)
+    assert a["rgb_map.npy"].shape == (256, 3) and a["grad_flat.npy"].shape == (2 * 595844,)
+    for name in a:
+        assert a[name].dtype == np.float32 and np.isfinite(a[name]).all(), name
+        np.testing.assert_allclose(a[name], b[name], rtol=1e-5, atol=1e-6, err_msg=name)
+    assert np.abs(a["grad_flat.npy"]).max() > 0
+
+
+@pytest.mark.gpu
 def test_gpu_bench_measures_its_hbm_traffic_in_the_run(tmp_path):
     """`roofline.traffic` and `step_traffic_bytes` come from two rocprofv3 counter passes started BY this bench run (one
     counter per pass, --kernel-trace only), not from a committed file: at 512 rays the dominant launch (fine forward or fine
     data gradients, 98 304 samples) must have moved about its workspace (10.4 / 10.1 KB per sample), and a step 40-odd KB per
     sample."""
     detail = str(tmp_path / "detail.json")
-    line = _run_bench(["--steps", "2", "--warmup", "1", "--no-cpu", "--no-extras", "--rays", "512", "--detail", detail], timeout=900)
+    line = _run_bench(["--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--no-extras", "--rays", "512", "--detail", detail],
+                      timeout=900)
     roof = line["roofline"]
     full = json.load(open(detail))["roofline"]
     assert roof.get("traffic_measured_live") is True, full.get("traffic_live_note") or full.get("traffic_source")
@@ -165,6 +187,31 @@ def test_gpu_bench_measures_its_hbm_traffic_in_the_run(tmp_path):
     assert 0.8 * 10000 * P < roof["traffic"] < 1.5 * 10400 * P, roof
     assert 30e3 * 512 * 256 < roof["step_traffic_bytes"] < 60e3 * 512 * 256, roof
     assert "rocprofv3" in full["traffic_source"] and full["traffic_pass_seconds"] < 300
+
+
+def test_dumped_outputs_stay_within_the_limit(tmp_path):
+    """--dump-outputs' writer: float32 (float64 kept), one .npy per array; past the limit every array keeps a share of
+    it proportional to its size, the same elements on every call"""
+    import numpy as np
+    import torch
+    import bench
+    arrays = {"big": torch.arange(40000, dtype=torch.float32).reshape(200, 200), "small": torch.ones(7, dtype=torch.float16),
+              "wide": torch.linspace(0, 1, 1000, dtype=torch.float64), "count": 3}
+    names = bench.write_outputs(str(tmp_path / "all"), arrays)
+    assert names == ["big", "small", "wide"]
+    got = {n: np.load(tmp_path / "all" / (n + ".npy")) for n in names}
+    assert got["big"].shape == (200, 200) and got["small"].dtype == np.float32 and got["wide"].dtype == np.float64
+    np.testing.assert_array_equal(got["big"], arrays["big"].numpy())
+    limit = 1024 * 3 + 40000                                           # about a quarter of the 164 KB
+    for k in range(2):
+        bench.write_outputs(str(tmp_path / ("s%d" % k)), arrays, limit=limit)
+    files = sorted((tmp_path / "s0").iterdir())
+    assert sum(f.stat().st_size for f in files) <= limit
+    for f in files:
+        x, y = np.load(f), np.load(tmp_path / "s1" / f.name)
+        np.testing.assert_array_equal(x, y)
+    big = np.load(tmp_path / "s0" / "big.npy")
+    assert 0 < big.size < 40000 and (np.diff(big) > 0).all()             # a sample, in index order
 
 
 # ---- first contact at N > 1 must fail LOUDLY, never hang (no GPU needed: the failures happen before any kernel) ----------
@@ -259,7 +306,7 @@ def test_gpu_two_rccl_ranks_on_one_device_end_with_a_line_not_a_hang():
         env.pop(k, None)
     t0 = time.time()
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "nccl", "--one-device",
-                        "--init-timeout", "90", "--steps", "2", "--warmup", "1", "--no-cpu", "--rays", "256"],
+                        "--init-timeout", "90", "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--rays", "256"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, env=env, cwd=ROOT)
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, (r.stdout[-1000:], r.stderr[-3000:])

@@ -64,6 +64,16 @@ def _prepare(mod, tmp_path, n_iters, extra=(), device="cpu", n_rand=8):
     return argv
 
 
+@pytest.fixture(autouse=True)
+def _restore_matrix_node_default():
+    """dropin.install() opts the camera model class into the shared K / E node for the rest of the process; later tests in
+    the same worker (tests/test_emu_camera.py) expect the package default back."""
+    from scnerf_amd import camera_model
+    saved = camera_model._PinholeRotNoise.__dict__.get("share_matrix_node")
+    yield
+    camera_model._PinholeRotNoise.share_matrix_node = saved
+
+
 @needs_reference
 def test_unmodified_run_nerf_imports_and_resolves_every_name():
     mod = S.import_reference_run_nerf()
