@@ -326,7 +326,9 @@ int scnerf_h3_pack(const float* flat_params, const int* jobs, const int* idx_fwd
 int scnerf_mlp_fwd_h3(int pt_dims, const float* pts, const float* viewdirs, int vd_stride, int samples_per_ray,
                       const float* wpacked, const short* stream_fwd, const float* scales, float* raw, float* save,
                       long long n_samples, float* chunk_amax, int n_chunks, long long chunk_samples, void* stream);
-/* scnerf_mlp_bwd in the resident arithmetic; wpacked_bwd: the packed fp32 backward buffer (its density-head table). */
+/* scnerf_mlp_bwd in the resident arithmetic; wpacked_bwd: the packed fp32 backward buffer (its density-head table).
+ * d_pts == d_views == NULL: no input gradient (the points and directions are data) -- the products that only feed it
+ * are not computed; grads and chunk_amax are bit-identical to the call with both.  Exactly one of them NULL: an error. */
 int scnerf_mlp_bwd_h3(int pt_dims, const float* d_raw, const float* pts, const float* viewdirs, int vd_stride,
                       int samples_per_ray, const float* wpacked_bwd, const short* stream_bwd, const float* scales,
                       const float* save, float* grads, float* d_pts, float* d_views, long long n_samples,

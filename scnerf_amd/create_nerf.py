@@ -52,13 +52,16 @@ class _QueryFunction(torch.autograd.Function):
     def backward(ctx, g_raw):
         p, v, spr, save, wbk, shape, vshape, planes, maxima = ctx.state
         d_raw = g_raw.reshape(-1, 4).contiguous().float()
-        grads, d_pts, d_views = ops.mlp_bwd(d_raw, p, v, spr, wbk, save, planes=planes, maxima=maxima)
+        # points and directions that are data need no gradient: the resident kernel then leaves d_pts / d_views out
+        input_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        grads, d_pts, d_views = ops.mlp_bwd(d_raw, p, v, spr, wbk, save, planes=planes, maxima=maxima, input_grad=input_grad)
         flat_grad = ops.nerf_wgrad(save, grads, d_raw, p.shape[0], maxima=maxima)
-        d_v = d_views.view(-1, spr, 3).sum(1).view(vshape)
+        d_p = d_pts.view(shape) if input_grad else None
+        d_v = d_views.view(-1, spr, 3).sum(1).view(vshape) if input_grad else None
         gs = [flat_grad[ML.PARAM_OFFSETS[n]: ML.PARAM_OFFSETS[n] + int(torch.Size(s).numel())].view(s)
               for n, s in ML.PARAM_SHAPES]
         ctx.state = None
-        return (d_pts.view(shape), d_v, None, None, *gs)
+        return (d_p, d_v, None, None, *gs)
 
 
 def _fused_applies(net, embed_fn, embeddirs_fn, viewdirs_given=True) -> bool:

@@ -120,7 +120,11 @@ __host__ __device__ constexpr unsigned bwd_lds_bytes() {
     return (unsigned)(kStreamLds + 256 * 4 + Var<PD>::kES * kThreads * 4);
 }
 
-template <int PD>
+// IG: the input gradient (d pts, d viewdirs) as well.  Without it (the points and directions are data) the products
+// that only feed it -- the encoded-direction rows of the views layer, the encoded-point columns of the skip layer and
+// of layer 0 -- are passed over (skip_units: the stream advances, no MFMA), the encoding's gradient is not formed and
+// d_pts / d_views are not touched; every dZ section and every chunk maximum is computed exactly as with it.
+template <int PD, bool IG>
 __global__ __launch_bounds__(kThreads, 1) void mlp_bwd_h3_kernel(
     const float* __restrict__ d_raw, const float* __restrict__ pts, const float* __restrict__ viewdirs, int vd_stride,
     int samples_per_ray, const float* __restrict__ wbk, const short* __restrict__ wh3, const float* __restrict__ sc,
@@ -209,7 +213,12 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_bwd_h3_kernel(
         constexpr int s = decltype(s_tag)::value;
         xh = bh[1][s]; xl = bl[1][s];
     };
-    {
+    if constexpr (!IG) {
+        skip_units<2, 4>(w, NoFill{});
+        const long ray = (long)((unsigned)pc / (unsigned)samples_per_ray);
+        note_chunk_max(11, fmaxf(fmaxf(1.f, fabsf(viewdirs[ray * vd_stride + 0])),
+                                 fmaxf(fabsf(viewdirs[ray * vd_stride + 1]), fabsf(viewdirs[ray * vd_stride + 2]))));
+    } else {
         f32x16 acce[2];
         tile_single<2, 4>(w, acce, hv_operand, NoFill{});
         const float os = inv_pow2(epiv.s_next) * scale_of(kLayerViews, kSwInv);
@@ -287,22 +296,27 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_bwd_h3_kernel(
             constexpr int s = decltype(s_tag)::value;
             xh = bh[1][s]; xl = bl[1][s];
         };
-        tile_pair<6, 16>(w, acc[0], operand, [&](auto sg) { epi_slot<GateEpi, 3, decltype(sg)::value, 9>(prev, acc[1], bh[1], bl[1]); });
-        const float os5 = inv_pow2(prev.s_next) * scale_of(5, kSwInv);
-        auto park_pair = [&](auto t0_tag, f32x16 (&a)[2]) {
-            constexpr int T0 = decltype(t0_tag)::value;
+        if constexpr (!IG) {
+            skip_units<6, 16>(w, [&](auto sg) { epi_slot<GateEpi, 3, decltype(sg)::value, 9>(prev, acc[1], bh[1], bl[1]); });
+            if constexpr (ET == 4) skip_units<22, 16>(w, NoFill{});
+        } else {
+            tile_pair<6, 16>(w, acc[0], operand, [&](auto sg) { epi_slot<GateEpi, 3, decltype(sg)::value, 9>(prev, acc[1], bh[1], bl[1]); });
+            const float os5 = inv_pow2(prev.s_next) * scale_of(5, kSwInv);
+            auto park_pair = [&](auto t0_tag, f32x16 (&a)[2]) {
+                constexpr int T0 = decltype(t0_tag)::value;
 #pragma unroll
-            for (int x = 0; x < 2; ++x)
-                if (16 * (T0 + x) < ES) {
+                for (int x = 0; x < 2; ++x)
+                    if (16 * (T0 + x) < ES) {
 #pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        park[(4 * (T0 + x) + q) * kThreads] = f32x4{a[x][4 * q] * os5, a[x][4 * q + 1] * os5, a[x][4 * q + 2] * os5, a[x][4 * q + 3] * os5};
-                }
-        };
-        park_pair(I<0>{}, acc[0]);
-        if constexpr (ET == 4) {
-            tile_pair<22, 16>(w, acc[1], operand, NoFill{});
-            park_pair(I<2>{}, acc[1]);
+                        for (int q = 0; q < 4; ++q)
+                            park[(4 * (T0 + x) + q) * kThreads] = f32x4{a[x][4 * q] * os5, a[x][4 * q + 1] * os5, a[x][4 * q + 2] * os5, a[x][4 * q + 3] * os5};
+                    }
+            };
+            park_pair(I<0>{}, acc[0]);
+            if constexpr (ET == 4) {
+                tile_pair<22, 16>(w, acc[1], operand, NoFill{});
+                park_pair(I<2>{}, acc[1]);
+            }
         }
         GateEpi cur = make_gate(5, prev.s_next, 4, kGradDz + 4 * 256, 256);
         const float am5 = amax_of(prev.am);
@@ -325,7 +339,13 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_bwd_h3_kernel(
         prev = cur2;
     }
     // ---- layer 0^T: d encoded point += W_0^T dZ_0, then the encoding's own gradient -> d pts ----
-    {
+    if constexpr (!IG) {
+        epi_all<GateEpi, 3>(prev, acc[1], bh[0], bl[0]);     // dZ_0's last pair: nothing left to hide it under
+        note_chunk_max(9, amax_of(prev.am));
+        float am_e = fmaxf(fmaxf(1.f, fabsf(pts[pc * PD + 0])), fmaxf(fabsf(pts[pc * PD + 1]), fabsf(pts[pc * PD + 2])));
+        if constexpr (PD == 4) am_e = fmaxf(am_e, fabsf(pts[pc * PD + 3]));
+        note_chunk_max(10, am_e);
+    } else {
         auto operand = [&](auto s_tag, u32x4& xh, u32x4& xl) {
             constexpr int s = decltype(s_tag)::value;
             xh = bh[0][s]; xl = bl[0][s];
@@ -375,16 +395,27 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_bwd_h3_kernel(
 }
 
 
+template <int PD, bool IG>
+inline int launch_bwd_h3_as(const float* d_raw, const float* pts, const float* viewdirs, int vd_stride, int samples_per_ray,
+                            const float* wpacked_bwd, const short* stream_bwd, const float* scales, const float* save,
+                            float* grads, float* d_pts, float* d_views, long long n_samples, ChunkMaxima cm, hipStream_t st) {
+    constexpr unsigned lds = bwd_lds_bytes<PD>();
+    SCN_LDS_OPT_IN((mlp_bwd_h3_kernel<PD, IG>), lds);
+    hipLaunchKernelGGL((mlp_bwd_h3_kernel<PD, IG>), dim3(scn_ceil_div(n_samples, kSamplesPerBlock)), dim3(kThreads), lds, st,
+                       d_raw, pts, viewdirs, vd_stride, samples_per_ray, wpacked_bwd, stream_bwd, scales, save, grads, d_pts,
+                       d_views, (long)n_samples, cm);
+    return scn_launch_status();
+}
+
+// d_pts == d_views == nullptr: no input gradient
 template <int PD>
 inline int launch_bwd_h3(const float* d_raw, const float* pts, const float* viewdirs, int vd_stride, int samples_per_ray,
                          const float* wpacked_bwd, const short* stream_bwd, const float* scales, const float* save,
                          float* grads, float* d_pts, float* d_views, long long n_samples, ChunkMaxima cm, hipStream_t st) {
-    constexpr unsigned lds = bwd_lds_bytes<PD>();
-    SCN_LDS_OPT_IN((mlp_bwd_h3_kernel<PD>), lds);
-    hipLaunchKernelGGL((mlp_bwd_h3_kernel<PD>), dim3(scn_ceil_div(n_samples, kSamplesPerBlock)), dim3(kThreads), lds, st,
-                       d_raw, pts, viewdirs, vd_stride, samples_per_ray, wpacked_bwd, stream_bwd, scales, save, grads, d_pts,
-                       d_views, (long)n_samples, cm);
-    return scn_launch_status();
+    return d_pts ? launch_bwd_h3_as<PD, true>(d_raw, pts, viewdirs, vd_stride, samples_per_ray, wpacked_bwd, stream_bwd, scales,
+                                              save, grads, d_pts, d_views, n_samples, cm, st)
+                 : launch_bwd_h3_as<PD, false>(d_raw, pts, viewdirs, vd_stride, samples_per_ray, wpacked_bwd, stream_bwd, scales,
+                                               save, grads, nullptr, nullptr, n_samples, cm, st);
 }
 
 

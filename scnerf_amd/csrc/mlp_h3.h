@@ -226,6 +226,28 @@ __device__ __forceinline__ void tile_single(Wave& w, f32x16 (&acc)[2], Operand&&
     });
 }
 
+// NU units of the stream passed over without their MFMAs (a product whose result nobody reads): the stream's slots and
+// barriers as in unit(), fill(I<sigma>) in slot sigma = 6 u + j, and the fragments of the unit after the last one
+// fetched into the ring.  The units that follow keep their compile-time phase U0 + NU.
+template <int U0, int NU, class Fill>
+__device__ __forceinline__ void skip_units(Wave& w, Fill&& fill) {
+    static_for<NU>([&](auto u_tag) {
+        constexpr int u = decltype(u_tag)::value;
+        constexpr int PH = (U0 + u) & 7, RP = (U0 + u) & 1;
+        static_for<6>([&](auto j_tag) {
+            constexpr int j = decltype(j_tag)::value;
+            stream_slot<PH * 6 + j>(w.ws, w.lds, w.tid16);
+            fill(I<6 * u + j>{});
+            if constexpr (u == NU - 1 && j < 4) {
+                constexpr int NPH = (PH + 1) & 7;
+                const unsigned buf = PH == 7 ? w.ws.next() : w.ws.cur;
+                w.ring[RP ^ 1][j] = *reinterpret_cast<const s16x8*>(w.lds + buf + (NPH * 4 + j) * 1024 + w.lane16);
+            }
+            sched_fence();
+        });
+    });
+}
+
 // ---- epilogue slices ------------------------------------------------------------------------------------------------
 // An epilogue works on one output-tile pair (tiles 2 P, 2 P + 1 of its layer) in eight PIECES -- (tile x, quarter q):
 // four accumulator registers = one 16-byte piece of the tile-native section = half of a K slab's lane operand -- and a

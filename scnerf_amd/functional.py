@@ -142,12 +142,16 @@ class RenderRaysFunction(torch.autograd.Function):
     @staticmethod
     def _stage_dgrad(stage, rays, spr, wbk, white_bkgd, g_rgb, g_disp, g_acc, g_depth, g_raw, d_rays, accumulate,
                      planes=None):
-        """Data gradients of one stage (compositing, network, rays); -> what its weight gradients need."""
+        """Data gradients of one stage (compositing, network, rays); -> what its weight gradients need.
+        d_rays None: the rays need no gradient -- neither the network's input gradient nor the ray reduction runs."""
         z, pts, raw, noise, save, maxima = stage
+        want = d_rays is not None
         d_raw, d_rd = ops.composite_bwd(raw, z, rays, noise, white_bkgd, _c(g_rgb), _c(g_disp), _c(g_acc),
-                                        _c(g_depth), _c(g_raw))
-        grads, d_pts, d_views = ops.mlp_bwd(d_raw, pts, rays[:, 8:11], spr, wbk, save, planes=planes, maxima=maxima)
-        ops.ray_reduce(d_pts, d_views, z, d_rd, d_rays, accumulate)
+                                        _c(g_depth), _c(g_raw), want_d_rays_d=want)
+        grads, d_pts, d_views = ops.mlp_bwd(d_raw, pts, rays[:, 8:11], spr, wbk, save, planes=planes, maxima=maxima,
+                                            input_grad=want)
+        if want:
+            ops.ray_reduce(d_pts, d_views, z, d_rd, d_rays, accumulate)
         return save, grads, d_raw, z.shape[0] * spr, maxima
 
     @staticmethod
@@ -166,7 +170,8 @@ class RenderRaysFunction(torch.autograd.Function):
             raise RuntimeError("render_rays was evaluated without gradient tracking")
         cfg, rays, n = ctx.cfg, ctx.rays, ctx.n
         sc, sf = cfg.n_samples, cfg.n_importance
-        d_rays = torch.zeros_like(rays)
+        # rays that are data (no requires_grad) get no gradient: autograd would drop it
+        d_rays = torch.zeros_like(rays) if ctx.needs_input_grad[0] else None
         fg_c = fg_f = None
         wrote = False
         # networks whose .grad tensors are views of one flat buffer take their weight gradients by direct

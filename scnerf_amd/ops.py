@@ -597,12 +597,14 @@ def save_workspace(P: int, device, pd: int = 3) -> Tensor:
 
 
 def mlp_bwd(d_raw: Tensor, pts: Tensor, viewdirs: Tensor, samples_per_ray: int, wpacked_bwd: Tensor,
-            save: Tensor, pd: int = 3, planes: Optional[Tensor] = None, maxima: Optional["ChunkMaxima"] = None):
-    """-> (grads workspace, d_pts [P,pd], d_views [P,3]).  `planes`: as mlp_fwd."""
+            save: Tensor, pd: int = 3, planes: Optional[Tensor] = None, maxima: Optional["ChunkMaxima"] = None,
+            input_grad: bool = True):
+    """-> (grads workspace, d_pts [P,pd], d_views [P,3]).  `planes`: as mlp_fwd.  input_grad=False: d_pts / d_views
+    are not needed -- the resident kernel skips them and returns None for both (the fp32 kernel computes them anyway)."""
     if isinstance(planes, ResidentWeights):
         if planes.pd != pd:
             raise ValueError("resident weights of another network variant")
-        return mlp_bwd_resident(d_raw, pts, viewdirs, samples_per_ray, wpacked_bwd, planes, save, maxima)
+        return mlp_bwd_resident(d_raw, pts, viewdirs, samples_per_ray, wpacked_bwd, planes, save, maxima, input_grad)
     _f(d_raw, "d_raw"), _f(pts, "pts"), _f(wpacked_bwd, "wpacked_bwd"), _f(save, "save")
     vptr, vstride = _vd(viewdirs)
     lay = ML.layout(pd)
@@ -623,8 +625,9 @@ def mlp_bwd(d_raw: Tensor, pts: Tensor, viewdirs: Tensor, samples_per_ray: int, 
 
 
 def mlp_bwd_resident(d_raw: Tensor, pts: Tensor, viewdirs: Tensor, samples_per_ray: int, wpacked_bwd: Tensor,
-                     rw: ResidentWeights, save: Tensor, maxima: Optional[ChunkMaxima] = None):
-    """mlp_bwd in the resident arithmetic (csrc/mlp_bwd_h3.hip): one launch -> (grads workspace, d_pts, d_views)."""
+                     rw: ResidentWeights, save: Tensor, maxima: Optional[ChunkMaxima] = None, input_grad: bool = True):
+    """mlp_bwd in the resident arithmetic (csrc/mlp_bwd_h3.hip): one launch -> (grads workspace, d_pts, d_views);
+    input_grad=False: the instantiation without the input gradient, d_pts = d_views = None."""
     _f(d_raw, "d_raw"), _f(pts, "pts"), _f(wpacked_bwd, "wpacked_bwd"), _f(save, "save")
     vptr, vstride = _vd(viewdirs)
     pd = rw.pd
@@ -634,8 +637,8 @@ def mlp_bwd_resident(d_raw: Tensor, pts: Tensor, viewdirs: Tensor, samples_per_r
         raise ValueError("wpacked_bwd has the wrong size")
     dev = pts.device
     grads = torch.empty(ML.grad_floats(P), dtype=torch.float32, device=dev)
-    d_pts = torch.empty((P, pd), dtype=torch.float32, device=dev)
-    d_views = torch.empty((P, 3), dtype=torch.float32, device=dev)
+    d_pts = torch.empty((P, pd), dtype=torch.float32, device=dev) if input_grad else None
+    d_views = torch.empty((P, 3), dtype=torch.float32, device=dev) if input_grad else None
     with PROFILE.region("mlp_bwd_h3_kernel%s/P=%d" % ("" if pd == 3 else "/pd4", P), 2 * _MAC_PER_SAMPLE[pd] * P):
         if maxima is not None:
             maxima.scales = rw.scales
