@@ -356,6 +356,54 @@ int scnerf_fine_stage_fwd_h3(const float* rays, int ray_stride, const float* z_c
                              float* acc_map, float* depth_map, float* weights, int n_rays, int n_coarse, int n_importance,
                              float* chunk_amax, int n_chunks, long long chunk_samples, void* stream);
 
+/* The scale guard of the resident arithmetic (csrc/resident_guard.h): scnerf_mlp_fwd_h3, scnerf_coarse_stage_fwd_h3,
+ * scnerf_fine_stage_fwd_h3 and scnerf_mlp_bwd_h3 with a record -- the old entry points are these with three NULLs.  Every
+ * layer output cut at a bound-derived per-sample scale S (forward: layers 0 .. 7, feature, views; data-gradient chain: dZ of
+ * views, feature, 7 .. 0) is checked: a live sample with max|z| > 0 trips when m = exponent(max|z|) + exponent(S) falls
+ * outside [-3, 13), where the cut is no longer fp32 grade.  guard_flags: int [ceil(n_samples / 128)], guard_any: int [1]
+ * (both zeroed by the caller, both or neither) -- 1 for every 128-sample block holding a tripped sample / for a launch with
+ * one.  guard_report (or NULL; needs guard_flags): float [10][64] + [10][2], zeroed by the caller -- per layer the largest
+ * 256 - m over 64 slots, then the samples under / over the range.  The outputs are bit-identical to the call without. */
+int scnerf_mlp_fwd_h3_guarded(int pt_dims, const float* pts, const float* viewdirs, int vd_stride, int samples_per_ray,
+                              const float* wpacked, const short* stream_fwd, const float* scales, float* raw, float* save,
+                              long long n_samples, float* chunk_amax, int n_chunks, long long chunk_samples, int* guard_flags,
+                              int* guard_any, float* guard_report, void* stream);
+int scnerf_coarse_stage_fwd_h3_guarded(const float* rays, int ray_stride, const float* t_vals, const float* t_rand,
+                                       int lindisp, const float* wpacked, const short* stream_fwd, const float* scales,
+                                       float* save, const float* noise, int white_bkgd, float* z, float* pts, float* raw,
+                                       float* rgb_map, float* disp_map, float* acc_map, float* depth_map, float* weights,
+                                       int n_rays, int n_samples, float* chunk_amax, int n_chunks, long long chunk_samples,
+                                       int* guard_flags, int* guard_any, float* guard_report, void* stream);
+int scnerf_fine_stage_fwd_h3_guarded(const float* rays, int ray_stride, const float* z_c, const float* w_c, const float* u,
+                                     int u_row_stride, const float* wpacked, const short* stream_fwd, const float* scales,
+                                     float* save, const float* noise, int white_bkgd, float* z_f, float* pts_f,
+                                     float* z_samples, float* z_std, long long* inds, float* cdf, float* raw, float* rgb_map,
+                                     float* disp_map, float* acc_map, float* depth_map, float* weights, int n_rays,
+                                     int n_coarse, int n_importance, float* chunk_amax, int n_chunks,
+                                     long long chunk_samples, int* guard_flags, int* guard_any, float* guard_report,
+                                     void* stream);
+int scnerf_mlp_bwd_h3_guarded(int pt_dims, const float* d_raw, const float* pts, const float* viewdirs, int vd_stride,
+                              int samples_per_ray, const float* wpacked_bwd, const short* stream_bwd, const float* scales,
+                              const float* save, float* grads, float* d_pts, float* d_views, long long n_samples,
+                              float* chunk_amax, int n_chunks, long long chunk_samples, int* guard_flags, int* guard_any,
+                              float* guard_report, void* stream);
+/* The exact-fp32 re-run of what the guard flagged: scnerf_mlp_fwd, scnerf_coarse_stage_fwd and scnerf_mlp_bwd (same
+ * arguments, same workspaces) on the 128-sample blocks whose flag (guard_flags of the *_h3_guarded call, int
+ * [ceil(n_samples / 128)]) is nonzero -- each such block bit-identical to the ungated call's, every other block untouched.
+ * A persistent grid of max_workgroups workgroups (0: one per CU) walks the blocks; nothing flagged costs one launch and
+ * the flag reads. */
+int scnerf_mlp_fwd_gated(int pt_dims, const float* pts, const float* viewdirs, int vd_stride, int samples_per_ray,
+                         const float* wpacked, float* raw, float* save, long long n_samples, const int* flags,
+                         int max_workgroups, void* stream);
+int scnerf_coarse_stage_fwd_gated(const float* rays, int ray_stride, const float* t_vals, const float* t_rand,
+                                  int lindisp, const float* wpacked, float* save, const float* noise, int white_bkgd,
+                                  float* z, float* pts, float* raw, float* rgb_map, float* disp_map, float* acc_map,
+                                  float* depth_map, float* weights, int n_rays, int n_samples, const int* flags,
+                                  int max_workgroups, void* stream);
+int scnerf_mlp_bwd_gated(int pt_dims, const float* d_raw, const float* pts, const float* viewdirs, int vd_stride,
+                         int samples_per_ray, const float* wpacked_bwd, const float* save, float* grads, float* d_pts,
+                         float* d_views, long long n_samples, const int* flags, int max_workgroups, void* stream);
+
 /* ------------------------------------------------------------------ PRD loss --------- */
 
 /* Projected-ray-distance loss, proj_ray_dist_loss_single (model/ray_dist_loss.py:22-246) after its

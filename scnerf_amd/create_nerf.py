@@ -44,7 +44,9 @@ class _QueryFunction(torch.autograd.Function):
         else:
             wf, planes = ops.inference_packs(net, flat)       # (forward-only: packed once per weight version)
         maxima = ops.ChunkMaxima(p.shape[0], p.device) if (train and isinstance(planes, ops.ResidentWeights)) else None
-        raw = ops.mlp_fwd(p, v, spr, wf, save, planes=planes, maxima=maxima)
+        guards = ops.guard_records(p.device, [("query", p.shape[0])]) if isinstance(planes, ops.ResidentWeights) else {}
+        raw = ops.mlp_fwd(p, v, spr, wf, save, planes=planes, maxima=maxima, guard=guards.get("query"))
+        ctx.guard_bwd = guards.get("query_bwd")
         ctx.state = (p, v, spr, save, ops.pack_weights(flat, "bwd") if train else None, shape, viewdirs.shape, planes, maxima)
         return raw.view(*shape[:-1], 4)
 
@@ -54,7 +56,8 @@ class _QueryFunction(torch.autograd.Function):
         d_raw = g_raw.reshape(-1, 4).contiguous().float()
         # points and directions that are data need no gradient: the resident kernel then leaves d_pts / d_views out
         input_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        grads, d_pts, d_views = ops.mlp_bwd(d_raw, p, v, spr, wbk, save, planes=planes, maxima=maxima, input_grad=input_grad)
+        grads, d_pts, d_views = ops.mlp_bwd(d_raw, p, v, spr, wbk, save, planes=planes, maxima=maxima, input_grad=input_grad,
+                                            guard=ctx.guard_bwd)
         flat_grad = ops.nerf_wgrad(save, grads, d_raw, p.shape[0], maxima=maxima)
         d_p = d_pts.view(shape) if input_grad else None
         d_v = d_views.view(-1, spr, 3).sum(1).view(vshape) if input_grad else None

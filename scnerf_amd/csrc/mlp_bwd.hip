@@ -79,14 +79,15 @@ __device__ __forceinline__ void pe_backward(float x, float y, float z, float w, 
     }
 }
 
+// the work of workgroup-sized block `blk` (128 samples): the body of mlp_bwd_kernel and of its gated form
 template <int PD>
-__global__ __launch_bounds__(kThreads, 1) void mlp_bwd_kernel(
+__device__ __forceinline__ void bwd_block(
     const float* __restrict__ d_raw, const float* __restrict__ pts, const float* __restrict__ viewdirs,
     int vd_stride, int samples_per_ray, const float* __restrict__ wbk, const float* __restrict__ save,
-    float* __restrict__ grads, float* __restrict__ d_pts, float* __restrict__ d_views, long P) {
+    float* __restrict__ grads, float* __restrict__ d_pts, float* __restrict__ d_views, long P, long blk) {
     const int lane = lane_id();
     const int m = lane & 31, h = lane >> 5;
-    const long wave_tile = (long)blockIdx.x * 4 + wave_id();
+    const long wave_tile = blk * 4 + wave_id();
     const long p = wave_tile * kSamplesPerWave + m;
     const bool live = p < P;
     const long pc = live ? p : P - 1;
@@ -204,7 +205,43 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_bwd_kernel(
     }
 }
 
+template <int PD>
+__global__ __launch_bounds__(kThreads, 1) void mlp_bwd_kernel(
+    const float* __restrict__ d_raw, const float* __restrict__ pts, const float* __restrict__ viewdirs,
+    int vd_stride, int samples_per_ray, const float* __restrict__ wbk, const float* __restrict__ save,
+    float* __restrict__ grads, float* __restrict__ d_pts, float* __restrict__ d_views, long P) {
+    bwd_block<PD>(d_raw, pts, viewdirs, vd_stride, samples_per_ray, wbk, save, grads, d_pts, d_views, P, (long)blockIdx.x);
+}
+
+// the gated re-run of the resident scale guard (csrc/resident_guard.h; as mlp_fwd.hip's mlp_fwd_gated_kernel)
+template <int PD>
+__global__ __launch_bounds__(kThreads, 1) void mlp_bwd_gated_kernel(
+    const float* __restrict__ d_raw, const float* __restrict__ pts, const float* __restrict__ viewdirs,
+    int vd_stride, int samples_per_ray, const float* __restrict__ wbk, const float* __restrict__ save,
+    float* __restrict__ grads, float* __restrict__ d_pts, float* __restrict__ d_views, long P, const int* __restrict__ flags) {
+    const long n_blocks = (P + kSamplesPerBlock - 1) / kSamplesPerBlock;
+    for (long b = blockIdx.x; b < n_blocks; b += gridDim.x) {
+        if (uniform(flags[b]) == 0) continue;
+        bwd_block<PD>(d_raw, pts, viewdirs, vd_stride, samples_per_ray, wbk, save, grads, d_pts, d_views, P, b);
+        block_sync();
+    }
+}
+
 }  // namespace
+
+template <int PD>
+static int launch_bwd_gated(const float* d_raw, const float* pts, const float* viewdirs, int vd_stride, int samples_per_ray,
+                            const float* wpacked_bwd, const float* save, float* grads, float* d_pts, float* d_views,
+                            long long n_samples, const int* flags, int max_workgroups, hipStream_t st) {
+    const size_t lds = (size_t)kStreamBufs * kMaxChunkBwd * sizeof(float);
+    const long long n_blocks = scn_ceil_div(n_samples, kSamplesPerBlock);
+    const long long w = max_workgroups > 0 ? max_workgroups : 256;      // 0: one per CU of the MI355X
+    SCN_LDS_OPT_IN((mlp_bwd_gated_kernel<PD>), lds);
+    hipLaunchKernelGGL((mlp_bwd_gated_kernel<PD>), dim3((unsigned)(w < n_blocks ? w : n_blocks)), dim3(kThreads), lds, st,
+                       d_raw, pts, viewdirs, vd_stride, samples_per_ray, wpacked_bwd, save, grads, d_pts, d_views,
+                       (long)n_samples, flags);
+    return scn_launch_status();
+}
 
 template <int PD>
 static int launch_bwd(const float* d_raw, const float* pts, const float* viewdirs, int vd_stride, int samples_per_ray,
@@ -228,4 +265,18 @@ extern "C" int scnerf_mlp_bwd(int pt_dims, const float* d_raw, const float* pts,
     hipStream_t st = (hipStream_t)stream;
     return pt_dims == 3 ? launch_bwd<3>(d_raw, pts, viewdirs, vd_stride, samples_per_ray, wpacked_bwd, save, grads, d_pts, d_views, n_samples, st)
                         : launch_bwd<4>(d_raw, pts, viewdirs, vd_stride, samples_per_ray, wpacked_bwd, save, grads, d_pts, d_views, n_samples, st);
+}
+
+// scnerf_mlp_bwd on the blocks whose guard flag is set (csrc/resident_guard.h)
+extern "C" int scnerf_mlp_bwd_gated(int pt_dims, const float* d_raw, const float* pts, const float* viewdirs,
+                                    int vd_stride, int samples_per_ray, const float* wpacked_bwd, const float* save,
+                                    float* grads, float* d_pts, float* d_views, long long n_samples, const int* flags,
+                                    int max_workgroups, void* stream) {
+    SCN_RETURN_IF(!d_raw || !pts || !viewdirs || !wpacked_bwd || !save || !grads || !d_pts || !d_views || !flags, SCN_EINVAL);
+    SCN_RETURN_IF(samples_per_ray < 1 || vd_stride < 3 || n_samples < 0 || (pt_dims != 3 && pt_dims != 4), SCN_EINVAL);
+    SCN_RETURN_IF(max_workgroups < 0, SCN_EINVAL);
+    if (n_samples == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    return pt_dims == 3 ? launch_bwd_gated<3>(d_raw, pts, viewdirs, vd_stride, samples_per_ray, wpacked_bwd, save, grads, d_pts, d_views, n_samples, flags, max_workgroups, st)
+                        : launch_bwd_gated<4>(d_raw, pts, viewdirs, vd_stride, samples_per_ray, wpacked_bwd, save, grads, d_pts, d_views, n_samples, flags, max_workgroups, st);
 }

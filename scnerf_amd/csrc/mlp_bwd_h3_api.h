@@ -2,12 +2,15 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "resident_guard.h"
+
 namespace scn {
 namespace h3b {
 
 // Where the weight-gradient GEMMs' chunk maxima of the dZ operands go (wgrad256_half.h): amax [8][n_chunks], job j =
 // dZ of trunk layer j + 1 (j = 7: d feature); chunk = samples per weight-gradient workgroup.
-struct ChunkMaxima { float* amax; int n_chunks; long chunk; };
+// `guard`: the record of the scale guard (resident_guard.h; null pointers: no check).
+struct ChunkMaxima { float* amax; int n_chunks; long chunk; ResidentGuard guard; };
 
 int bwd_h3_pd3(const float* d_raw, const float* pts, const float* viewdirs, int vd_stride, int samples_per_ray,
                const float* wpacked_bwd, const short* stream_bwd, const float* scales, const float* save, float* grads,

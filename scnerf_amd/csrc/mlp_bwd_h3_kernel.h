@@ -174,6 +174,10 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_bwd_h3_kernel(
         v = fmaxf(v, shfl_xor(v, 2)); v = fmaxf(v, shfl_xor(v, 1));
         if (lane_id() == 0) atomic_max_nonneg(cm.amax + (long)job * cm.n_chunks + chunk_of_tile, v);
     };
+    // the scale guard (resident_guard.h); guard layer l names dZ of layer l (8: feature, 9: views)
+    auto guard = [&](int guard_layer, float am, float s) __attribute__((always_inline)) {
+        guard_check(cm.guard, guard_layer, am, s, live, wave_tile);
+    };
     using GateEpi = BwdEpi<0>;
     auto make_gate = [&](int layer, float s_in, int mask_sect, int out_offset, int out_width) {
         GateEpi e;
@@ -207,6 +211,7 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_bwd_h3_kernel(
     }
     const float am_v = amax_of(epiv.am);
     note_chunk_max(8, am_v);            // dZ of the views layer: the A operand of its weight-gradient GEMMs
+    guard(kLayerViews, am_v, epiv.s_next);
 
     // ---- views layer^T, encoded-direction rows first: d ev = (W_v^T)[256 ..] dZ_v -> d viewdirs ----
     auto hv_operand = [&](auto s_tag, u32x4& xh, u32x4& xl) {
@@ -265,6 +270,7 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_bwd_h3_kernel(
         tile_pair<6, 16>(w, acc[0], operand, [&](auto sg) { epi_slot<Pend, 3, decltype(sg)::value, 9>(pend, acc[1], bh[X], bl[X]); });
         const float am_in = amax_of(pend.am);              // the layer's operand (dZ of weight-gradient job `job`) is complete
         note_chunk_max(job, am_in);
+        guard(job == 7 ? kLayerFeat : job + 1, am_in, pend.s_next);
         cur.s_next = scale_for(__builtin_fmaf(bound_a, am_in, bound_extra));
         tile_pair<22, 16>(w, acc[1], operand, [&](auto sg) { epi_slot<Cur, 0, decltype(sg)::value, 12>(cur, acc[0], bh[X ^ 1], bl[X ^ 1]); });
         tile_pair<38, 16>(w, acc[0], operand, [&](auto sg) { epi_slot<Cur, 1, decltype(sg)::value, 12>(cur, acc[1], bh[X ^ 1], bl[X ^ 1]); });
@@ -321,6 +327,7 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_bwd_h3_kernel(
         GateEpi cur = make_gate(5, prev.s_next, 4, kGradDz + 4 * 256, 256);
         const float am5 = amax_of(prev.am);
         note_chunk_max(4, am5);
+        guard(5, am5, prev.s_next);
         cur.s_next = scale_for(scale_of(5, kBoundAT) * am5);
         constexpr int U0 = 6;          // (the encoded-point part is 16 or 32 units: the phase stays)
         tile_pair<U0, 16>(w, acc[0], operand, NoFill{});
@@ -342,6 +349,7 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_bwd_h3_kernel(
     if constexpr (!IG) {
         epi_all<GateEpi, 3>(prev, acc[1], bh[0], bl[0]);     // dZ_0's last pair: nothing left to hide it under
         note_chunk_max(9, amax_of(prev.am));
+        guard(0, amax_of(prev.am), prev.s_next);
         float am_e = fmaxf(fmaxf(1.f, fabsf(pts[pc * PD + 0])), fmaxf(fabsf(pts[pc * PD + 1]), fabsf(pts[pc * PD + 2])));
         if constexpr (PD == 4) am_e = fmaxf(am_e, fabsf(pts[pc * PD + 3]));
         note_chunk_max(10, am_e);
@@ -354,6 +362,7 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_bwd_h3_kernel(
         tile_pair<6, 16>(w, acc[0], operand, [&](auto sg) { epi_slot<GateEpi, 3, decltype(sg)::value, 9>(prev, acc[1], bh[0], bl[0]); });
         const float os0 = inv_pow2(prev.s_next) * scale_of(0, kSwInv);
         note_chunk_max(9, amax_of(prev.am));        // dZ of layer 0
+        guard(0, amax_of(prev.am), prev.s_next);
         auto add_pair = [&](auto t0_tag, f32x16 (&a)[2]) {
             constexpr int T0 = decltype(t0_tag)::value;
 #pragma unroll

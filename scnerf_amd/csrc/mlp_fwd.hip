@@ -104,14 +104,16 @@ constexpr int kCoarseSamples = 64;
 
 // TRAIN: also leave the activations / encodings / ReLU masks in `save` for the dgrad and wgrad kernels
 // COARSE: points come from `cs` (PD == 3, 64 samples per ray), `pts` is unused
-template <int PD, bool TRAIN, bool COARSE = false>
-__global__ __launch_bounds__(kThreads, 1) void mlp_fwd_kernel(
+// the work of workgroup-sized block `blk` (128 samples): the body of mlp_fwd_kernel and of its gated form
+template <int PD, bool TRAIN, bool COARSE>
+__device__ __forceinline__ void fwd_block(
     const float* __restrict__ pts, const float* __restrict__ viewdirs, int vd_stride, int samples_per_ray,
-    const float* __restrict__ wpk, float* __restrict__ raw, float* __restrict__ save_arg, long P, CoarseStage cs) {
+    const float* __restrict__ wpk, float* __restrict__ raw, float* __restrict__ save_arg, long P, const CoarseStage& cs,
+    long blk) {
     float* const save = TRAIN ? save_arg : nullptr;
     const int lane = lane_id();
     const int m = lane & 31, h = lane >> 5;
-    const long wave_tile = (long)blockIdx.x * 4 + wave_id();
+    const long wave_tile = blk * 4 + wave_id();
     const long p = wave_tile * kSamplesPerWave + m;
     const bool live = p < P;
     const long pc = live ? p : P - 1;
@@ -244,7 +246,7 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_kernel(
         block_sync();
         if (wave_id() < kSamplesPerBlock / kCoarseSamples) {                  // one wave per ray, lane = sample
             const int slot = wave_id();
-            long ray = (long)blockIdx.x * (kSamplesPerBlock / kCoarseSamples) + slot;
+            long ray = blk * (kSamplesPerBlock / kCoarseSamples) + slot;
             const bool ray_live = ray < cs.n_rays;
             if (!ray_live) ray = cs.n_rays - 1;
             const float norm = ray::ray_norm(cs.rays + ray * cs.ray_stride + 3);
@@ -256,6 +258,29 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_kernel(
                                cs.white_bkgd, ray_live, lane, cs.rgb + ray * 3, cs.disp + ray, cs.acc + ray,
                                cs.depth ? cs.depth + ray : nullptr, cs.weights ? cs.weights + ray * kCoarseSamples : nullptr);
         }
+    }
+}
+
+template <int PD, bool TRAIN, bool COARSE = false>
+__global__ __launch_bounds__(kThreads, 1) void mlp_fwd_kernel(
+    const float* __restrict__ pts, const float* __restrict__ viewdirs, int vd_stride, int samples_per_ray,
+    const float* __restrict__ wpk, float* __restrict__ raw, float* __restrict__ save_arg, long P, CoarseStage cs) {
+    fwd_block<PD, TRAIN, COARSE>(pts, viewdirs, vd_stride, samples_per_ray, wpk, raw, save_arg, P, cs, (long)blockIdx.x);
+}
+
+// The gated re-run of the resident scale guard (csrc/resident_guard.h): a persistent grid walks the blocks and runs
+// the unchanged block body on those whose flag is set -- bit-identical to mlp_fwd_kernel's samples there -- and skips
+// the others.  (A workgroup finishes a block's LDS reads before it starts the next one: the barrier behind it.)
+template <int PD, bool TRAIN, bool COARSE>
+__global__ __launch_bounds__(kThreads, 1) void mlp_fwd_gated_kernel(
+    const float* __restrict__ pts, const float* __restrict__ viewdirs, int vd_stride, int samples_per_ray,
+    const float* __restrict__ wpk, float* __restrict__ raw, float* __restrict__ save_arg, long P, CoarseStage cs,
+    const int* __restrict__ flags) {
+    const long n_blocks = (P + kSamplesPerBlock - 1) / kSamplesPerBlock;
+    for (long b = blockIdx.x; b < n_blocks; b += gridDim.x) {
+        if (uniform(flags[b]) == 0) continue;
+        fwd_block<PD, TRAIN, COARSE>(pts, viewdirs, vd_stride, samples_per_ray, wpk, raw, save_arg, P, cs, b);
+        block_sync();
     }
 }
 
@@ -313,6 +338,36 @@ static int launch_fwd(const float* pts, const float* viewdirs, int vd_stride, in
     return scn_launch_status();
 }
 
+// workgroups of a gated launch: max_workgroups, 0 = one per CU of the MI355X; never more than the blocks
+constexpr int kCUs = 256;
+static int gated_grid(long long n_blocks, int max_workgroups) {
+    const long long w = max_workgroups > 0 ? max_workgroups : kCUs;
+    return (int)(w < n_blocks ? w : n_blocks);
+}
+
+template <int PD, bool TRAIN>
+static int launch_fwd_gated(const float* pts, const float* viewdirs, int vd_stride, int samples_per_ray, const float* wpacked,
+                            float* raw, float* save, long long n_samples, const int* flags, int max_workgroups, hipStream_t st) {
+    const size_t lds = (size_t)(kStreamBufs * kMaxChunkFwd + Var<PD>::kES * kThreads) * sizeof(float);
+    SCN_LDS_OPT_IN((mlp_fwd_gated_kernel<PD, TRAIN, false>), lds);
+    hipLaunchKernelGGL((mlp_fwd_gated_kernel<PD, TRAIN, false>), dim3(gated_grid(scn_ceil_div(n_samples, kSamplesPerBlock), max_workgroups)),
+                       dim3(kThreads), lds, st, pts, viewdirs, vd_stride, samples_per_ray, wpacked, raw, save, (long)n_samples,
+                       CoarseStage{}, flags);
+    return scn_launch_status();
+}
+
+template <bool TRAIN>
+static int launch_coarse_stage_gated(const CoarseStage& cs, const float* wpacked, float* raw, float* save, const int* flags,
+                                     int max_workgroups, hipStream_t st) {
+    const size_t lds = (size_t)(kStreamBufs * kMaxChunkFwd + Var<3>::kES * kThreads) * sizeof(float);
+    const long P = (long)cs.n_rays * kCoarseSamples;
+    SCN_LDS_OPT_IN((mlp_fwd_gated_kernel<3, TRAIN, true>), lds);
+    hipLaunchKernelGGL((mlp_fwd_gated_kernel<3, TRAIN, true>), dim3(gated_grid(scn_ceil_div(P, kSamplesPerBlock), max_workgroups)),
+                       dim3(kThreads), lds, st, (const float*)nullptr, cs.rays + 8, cs.ray_stride, kCoarseSamples, wpacked, raw,
+                       save, P, cs, flags);
+    return scn_launch_status();
+}
+
 template <bool TRAIN>
 static int launch_coarse_stage(const CoarseStage& cs, const float* wpacked, float* raw, float* save, hipStream_t st) {
     const size_t lds = (size_t)(kStreamBufs * kMaxChunkFwd + Var<3>::kES * kThreads) * sizeof(float);
@@ -350,4 +405,35 @@ extern "C" int scnerf_mlp_fwd(int pt_dims, const float* pts, const float* viewdi
                     : launch_fwd<3, false>(pts, viewdirs, vd_stride, samples_per_ray, wpacked, raw, save, n_samples, st);
     return save ? launch_fwd<4, true>(pts, viewdirs, vd_stride, samples_per_ray, wpacked, raw, save, n_samples, st)
                 : launch_fwd<4, false>(pts, viewdirs, vd_stride, samples_per_ray, wpacked, raw, save, n_samples, st);
+}
+
+// scnerf_coarse_stage_fwd / scnerf_mlp_fwd on the blocks whose guard flag is set (csrc/resident_guard.h)
+extern "C" int scnerf_coarse_stage_fwd_gated(const float* rays, int ray_stride, const float* t_vals, const float* t_rand,
+                                             int lindisp, const float* wpacked, float* save, const float* noise,
+                                             int white_bkgd, float* z, float* pts, float* raw, float* rgb_map,
+                                             float* disp_map, float* acc_map, float* depth_map, float* weights, int n_rays,
+                                             int n_samples, const int* flags, int max_workgroups, void* stream) {
+    SCN_RETURN_IF(!rays || !t_vals || !wpacked || !z || !pts || !raw || !rgb_map || !disp_map || !acc_map || !flags, SCN_EINVAL);
+    SCN_RETURN_IF(n_rays < 0 || ray_stride < 11 || max_workgroups < 0, SCN_EINVAL);
+    SCN_RETURN_IF(n_samples != kCoarseSamples, SCN_ENOSUP);
+    if (n_rays == 0) return 0;
+    const CoarseStage cs{rays, ray_stride, n_rays, t_vals, t_rand, lindisp, z, pts, noise, white_bkgd,
+                         rgb_map, disp_map, acc_map, depth_map, weights};
+    hipStream_t st = (hipStream_t)stream;
+    return save ? launch_coarse_stage_gated<true>(cs, wpacked, raw, save, flags, max_workgroups, st)
+                : launch_coarse_stage_gated<false>(cs, wpacked, raw, save, flags, max_workgroups, st);
+}
+
+extern "C" int scnerf_mlp_fwd_gated(int pt_dims, const float* pts, const float* viewdirs, int vd_stride, int samples_per_ray,
+                                    const float* wpacked, float* raw, float* save, long long n_samples, const int* flags,
+                                    int max_workgroups, void* stream) {
+    SCN_RETURN_IF(!pts || !viewdirs || !wpacked || !raw || !flags || samples_per_ray < 1 || vd_stride < 3 || n_samples < 0, SCN_EINVAL);
+    SCN_RETURN_IF((pt_dims != 3 && pt_dims != 4) || max_workgroups < 0, SCN_EINVAL);
+    if (n_samples == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (pt_dims == 3)
+        return save ? launch_fwd_gated<3, true>(pts, viewdirs, vd_stride, samples_per_ray, wpacked, raw, save, n_samples, flags, max_workgroups, st)
+                    : launch_fwd_gated<3, false>(pts, viewdirs, vd_stride, samples_per_ray, wpacked, raw, save, n_samples, flags, max_workgroups, st);
+    return save ? launch_fwd_gated<4, true>(pts, viewdirs, vd_stride, samples_per_ray, wpacked, raw, save, n_samples, flags, max_workgroups, st)
+                : launch_fwd_gated<4, false>(pts, viewdirs, vd_stride, samples_per_ray, wpacked, raw, save, n_samples, flags, max_workgroups, st);
 }

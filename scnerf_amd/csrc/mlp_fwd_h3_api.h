@@ -5,12 +5,15 @@
 
 #include <hip/hip_runtime.h>
 
+#include "resident_guard.h"
+
 namespace scn {
 namespace h3f {
 
 // Where the weight-gradient GEMMs' chunk maxima go (wgrad256_half.h): amax [8][n_chunks], job j = the GEMM whose X
 // operand is the input of trunk layer j + 1 (j = 7: feature_linear); chunk = samples per weight-gradient workgroup.
-struct ChunkMaxima { float* amax; int n_chunks; long chunk; };
+// `guard`: the record of the scale guard (resident_guard.h; null pointers: no check).
+struct ChunkMaxima { float* amax; int n_chunks; long chunk; ResidentGuard guard; };
 
 struct CoarseStage {
     const float* rays; int ray_stride; int n_rays;

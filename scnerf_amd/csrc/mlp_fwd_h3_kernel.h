@@ -320,6 +320,14 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_h3_kernel(
         }
     };
 
+    // the scale guard (resident_guard.h): its record read from the argument block where it is used
+    auto guard = [&](int guard_layer, float am, float s) __attribute__((always_inline)) {
+        const FwdKernelArgs mirror{pts, viewdirs, vd_stride, samples_per_ray, wpk, wh3, sc, raw, save_arg, P, cs, fs, cm};
+        const auto* late = late_args(mirror);
+        const ResidentGuard g{late->cm.guard.flags, late->cm.guard.any, late->cm.guard.report};
+        guard_check(g, guard_layer, am, s, lane_now().live, wave_tile);
+    };
+
     using Relu = FwdEpi<TRAIN, 0>;
     auto make_relu = [&](int l, float s_in) {         // epilogue of trunk layer l whose input was cut at s_in
         Relu e;
@@ -374,6 +382,7 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_h3_kernel(
         // this layer's weight-gradient GEMM: job layer - 1, feature_linear: 7)
         const float am_in = amax_of(pend.am);
         note_chunk_max(layer == kLayerFeat ? 7 : layer - 1, am_in);
+        guard(layer == kLayerFeat ? 7 : layer - 1, am_in, pend.s_next);
         const float am = fmaxf(am_in, am_floor);
         cur.s_next = scale_for(fmaxf(__builtin_fmaf(scale_of(layer, kBoundA), am, scale_of(layer, kBoundB)), bound_floor));
         tile_pair<U0 + NK, NK>(w, acc[1], operand, [&](auto sg_tag) {
@@ -472,13 +481,16 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_h3_kernel(
         tile_pair<0, 18>(w, acc[0], operand, [&](auto sg_tag) {
             epi_slot<FwdEpi<TRAIN, 2>, 3, decltype(sg_tag)::value, 9>(epif, acc[1], bh[0], bl[0]);
         });
-        const float am = fmaxf(amax_of(epif.am), m_ev);
+        const float am_f = amax_of(epif.am);
+        guard(kLayerFeat, am_f, epif.s_next);
+        const float am = fmaxf(am_f, m_ev);
         epiv.s_next = scale_for(__builtin_fmaf(scale_of(kLayerViews, kBoundA), am, scale_of(kLayerViews, kBoundB)));
         tile_pair<18, 18>(w, acc[1], operand, [&](auto sg_tag) {
             epi_slot<Relu, 0, decltype(sg_tag)::value, 12>(epiv, acc[0], bh[1], bl[1]);
         });
         epi_all<Relu, 1>(epiv, acc[1], bh[1], bl[1]);
         store_mask(epiv, 8);
+        guard(kLayerViews, amax_of(epiv.am), epiv.s_next);
     }
 
     // ---- rgb: one output tile over the 128 views-layer activations (stream units 36 .. 39) ----

@@ -49,6 +49,7 @@
 #include <scn_wave.h>
 
 #include "mlp_common.h"
+#include "resident_guard.h"
 
 namespace scn {
 namespace h3 {
@@ -80,6 +81,31 @@ __device__ __forceinline__ float scale_for(float bound) {
     return __uint_as_float((266u - (e < 13u ? 13u : e)) << 23);
 }
 __device__ __forceinline__ float inv_pow2(float s) { return __uint_as_float(0x7f000000u - __float_as_uint(s)); }
+
+// The scale guard (resident_guard.h) on one layer output of the wave's samples: `am` the sample's measured max|z| (both
+// lane halves hold it), `s` the power of two that output was cut at.  Nothing without a record.
+__device__ __forceinline__ void guard_check(const ResidentGuard& g, int guard_layer, float am, float s, bool live, long wave_tile) {
+    if (g.flags == nullptr) return;
+    const int m = (int)((__float_as_uint(am) >> 23) & 0xffu) + (int)((__float_as_uint(s) >> 23) & 0xffu) - 254;
+    const bool on = live && lane_id() < 32 && am > 0.f;
+    const unsigned long long under = ballot(on && m < kGuardLo), over = ballot(on && m >= kGuardHi);
+    if ((under | over) != 0ull && lane_id() == 0) {
+        g.flags[wave_tile >> 2] = 1;
+        *g.any = 1;
+        if (g.report) {
+            float* counts = g.report + kGuardLayers * kGuardSlots + 2 * guard_layer;
+            if (under) atomic_add(counts, (float)popcount64(under));
+            if (over) atomic_add(counts + 1, (float)popcount64(over));
+        }
+    }
+    if (g.report) {
+        float v = on ? (float)(kGuardBias - m) : 0.f;
+        v = fmaxf(v, shfl_xor(v, 16)); v = fmaxf(v, shfl_xor(v, 8)); v = fmaxf(v, shfl_xor(v, 4));
+        v = fmaxf(v, shfl_xor(v, 2)); v = fmaxf(v, shfl_xor(v, 1));
+        if (lane_id() == 0 && v > 0.f)
+            atomic_max_nonneg(g.report + guard_layer * kGuardSlots + (int)(wave_tile & (kGuardSlots - 1)), v);
+    }
+}
 
 // x[0 .. 7] s -> the two planes of one K slab's lane operand
 __device__ __forceinline__ void cut8(const float* x, float s, u32x4& h, u32x4& l) {

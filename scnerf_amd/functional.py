@@ -86,14 +86,19 @@ class RenderRaysFunction(torch.autograd.Function):
         resident = isinstance(pl_c, ops.ResidentWeights)
         # (resident kernels, training: they leave the chunk maxima the fp16 weight-gradient GEMMs scale by)
         mx_c = ops.ChunkMaxima(n * sc, dev) if (train and resident) else None
+        # (the resident kernels' scale guard, ops.resident_guard: None while it is off)
+        # (one record buffer per call, every pass of both stages, forward and data gradients)
+        guards = ops.guard_records(dev, [("coarse", n * sc)] + ([("fine", n * (sc + sf))] if sf > 0 else [])) \
+            if (resident and n > 0) else {}
+        gd_c = guards.get("coarse")
         if sc == ops.COARSE_STAGE_SAMPLES and n > 0:
             # the whole coarse stage -- stratified depths, network, compositing -- is one launch
             z_c, pts_c, raw_c, rgb_c, disp_c, acc_c, w_c, depth_c = ops.coarse_stage_fwd(
                 rays, host_linspace(sc, dev), _c(t_rand), cfg.lindisp, wf_c, save_c, _c(noise_c), cfg.white_bkgd,
-                planes=pl_c, maxima=mx_c)
+                planes=pl_c, maxima=mx_c, guard=gd_c)
         else:
             z_c, pts_c = ops.coarse_sample(rays, host_linspace(sc, dev), _c(t_rand), cfg.lindisp)
-            raw_c = ops.mlp_fwd(pts_c, viewdirs, sc, wf_c, save_c, planes=pl_c, maxima=mx_c).view(n, sc, 4)
+            raw_c = ops.mlp_fwd(pts_c, viewdirs, sc, wf_c, save_c, planes=pl_c, maxima=mx_c, guard=gd_c).view(n, sc, 4)
             rgb_c, disp_c, acc_c, w_c, depth_c = ops.composite_fwd(raw_c, z_c, rays, _c(noise_c), cfg.white_bkgd)
 
         ctx.cfg, ctx.train, ctx.n = cfg, train, n
@@ -101,6 +106,7 @@ class RenderRaysFunction(torch.autograd.Function):
         ctx.n_params_c = len(net_c.ordered_parameters())
         ctx.coarse = (z_c, pts_c, raw_c, _c(noise_c), save_c, mx_c)
         ctx.pl_c = pl_c
+        ctx.guards = guards
         ctx.rays = rays
         ctx.wb_c = ops.pack_weights(flat_c, "bwd") if train else None
         ctx.fine = None
@@ -123,14 +129,16 @@ class RenderRaysFunction(torch.autograd.Function):
         else:
             wf_f, pl_f = ops.inference_packs(fine_net, flat_f)
         mx_f = ops.ChunkMaxima(n * tot, dev) if (train and resident) else None
-        if ops.fused_fine_stage() and resident and sc == ops.COARSE_STAGE_SAMPLES and sf in ops.FINE_STAGE_IMPORTANCE and n > 0:
+        gd_f = guards.get("fine")
+        # (with the guard on, the three launches: the same numbers as the fused stage)
+        if ops.fused_fine_stage() and gd_f is None and resident and sc == ops.COARSE_STAGE_SAMPLES and sf in ops.FINE_STAGE_IMPORTANCE and n > 0:
             # the whole fine stage -- inverse-cdf sampler, merge, network, compositing -- as one launch (opt-in: measured
             # slower than the three launches below, ops.fused_fine_stage)
             z_f, pts_f, z_s, z_std, _, _, raw_f, rgb_f, disp_f, acc_f, depth_f, _ = ops.fine_stage_fwd(
                 rays, z_c, w_c, u_dev, wf_f, save_f, _c(noise_f), cfg.white_bkgd, pl_f, maxima=mx_f)
         else:
             z_f, pts_f, z_s, z_std, _, _ = ops.fine_sample(rays, z_c, w_c, u_dev)
-            raw_f = ops.mlp_fwd(pts_f, viewdirs, tot, wf_f, save_f, planes=pl_f, maxima=mx_f).view(n, tot, 4)
+            raw_f = ops.mlp_fwd(pts_f, viewdirs, tot, wf_f, save_f, planes=pl_f, maxima=mx_f, guard=gd_f).view(n, tot, 4)
             rgb_f, disp_f, acc_f, _, depth_f = ops.composite_fwd(raw_f, z_f, rays, _c(noise_f), cfg.white_bkgd,
                                                                  want_weights=False)
         ctx.fine = (z_f, pts_f, raw_f, _c(noise_f), save_f, mx_f)
@@ -141,7 +149,7 @@ class RenderRaysFunction(torch.autograd.Function):
 
     @staticmethod
     def _stage_dgrad(stage, rays, spr, wbk, white_bkgd, g_rgb, g_disp, g_acc, g_depth, g_raw, d_rays, accumulate,
-                     planes=None):
+                     planes=None, guard=None):
         """Data gradients of one stage (compositing, network, rays); -> what its weight gradients need.
         d_rays None: the rays need no gradient -- neither the network's input gradient nor the ray reduction runs."""
         z, pts, raw, noise, save, maxima = stage
@@ -149,7 +157,7 @@ class RenderRaysFunction(torch.autograd.Function):
         d_raw, d_rd = ops.composite_bwd(raw, z, rays, noise, white_bkgd, _c(g_rgb), _c(g_disp), _c(g_acc),
                                         _c(g_depth), _c(g_raw), want_d_rays_d=want)
         grads, d_pts, d_views = ops.mlp_bwd(d_raw, pts, rays[:, 8:11], spr, wbk, save, planes=planes, maxima=maxima,
-                                            input_grad=want)
+                                            input_grad=want, guard=guard)
         if want:
             ops.ray_reduce(d_pts, d_views, z, d_rd, d_rays, accumulate)
         return save, grads, d_raw, z.shape[0] * spr, maxima
@@ -188,14 +196,14 @@ class RenderRaysFunction(torch.autograd.Function):
             if any(g is not None for g in (g_rgb, g_disp, g_acc, g_depth, g_raw)):
                 pend_f = RenderRaysFunction._stage_dgrad(ctx.fine, rays, sc + sf, ctx.wb_f, cfg.white_bkgd,
                                                          g_rgb, g_disp, g_acc, g_depth, g_raw, d_rays, wrote,
-                                                         planes=ctx.pl_f)
+                                                         planes=ctx.pl_f, guard=ctx.guards.get("fine_bwd"))
                 wrote = True
             coarse_g = (g_rgb0, g_disp0, g_acc0, g_depth0, None)
         else:
             coarse_g = (g_rgb, g_disp, g_acc, g_depth, g_raw)
         if any(g is not None for g in coarse_g):
             pend_c = RenderRaysFunction._stage_dgrad(ctx.coarse, rays, sc, ctx.wb_c, cfg.white_bkgd,
-                                                     *coarse_g, d_rays, wrote, planes=ctx.pl_c)
+                                                     *coarse_g, d_rays, wrote, planes=ctx.pl_c, guard=ctx.guards.get("coarse_bwd"))
         if pend_f is not None:
             fg_f = RenderRaysFunction._stage_wgrad(pend_f, into=into_f)
         if pend_c is not None:

@@ -77,8 +77,11 @@ class _NerfNetFunction(torch.autograd.Function):
         resident = train and isinstance(pl_f, ops.ResidentWeights)
         mx_f = ops.ChunkMaxima(n * sf, dev) if resident else None        # (for the fp16 weight-gradient GEMMs)
         mx_b = ops.ChunkMaxima(n * sb, dev) if resident else None
-        raw_f = ops.mlp_fwd(fg_pts, views, sf, wf_f, save_f, pd=3, planes=pl_f, maxima=mx_f)
-        raw_b = ops.mlp_fwd(bg_pts, views, sb, wf_b, save_b, pd=4, planes=pl_b, maxima=mx_b)
+        guards = ops.guard_records(dev, [("nerfpp_fg", n * sf), ("nerfpp_bg", n * sb)]) \
+            if (isinstance(pl_f, ops.ResidentWeights) and n > 0) else {}
+        raw_f = ops.mlp_fwd(fg_pts, views, sf, wf_f, save_f, pd=3, planes=pl_f, maxima=mx_f, guard=guards.get("nerfpp_fg"))
+        raw_b = ops.mlp_fwd(bg_pts, views, sb, wf_b, save_b, pd=4, planes=pl_b, maxima=mx_b, guard=guards.get("nerfpp_bg"))
+        ctx.guards = guards
         out = {"rgb": (n, 3), "fg_weights": (n, sf), "bg_weights": (n, sb), "fg_rgb": (n, 3), "fg_depth": (n,),
                "bg_rgb": (n, 3), "bg_depth": (n,), "bg_lambda": (n,)}
         t = {k: torch.empty(sh, dtype=torch.float32, device=dev) for k, sh in out.items()}
@@ -115,8 +118,10 @@ class _NerfNetFunction(torch.autograd.Function):
                                                  _p(d_norm), n, sf, sb, _stream()), "scnerf_npp_composite_bwd")
         # both networks' data gradients first, then both weight-gradient passes (one clock recovery after the bf16
         # weight-gradient GEMMs instead of two: functional.py)
-        grads_f, d_pts_f, d_views_f = ops.mlp_bwd(d_raw_f, fg_pts, views, sf, wb_f, save_f, pd=3, planes=pl_f, maxima=mx_f)
-        grads_b, d_pts_b, d_views_b = ops.mlp_bwd(d_raw_b, bg_pts, views, sb, wb_b, save_b, pd=4, planes=pl_b, maxima=mx_b)
+        grads_f, d_pts_f, d_views_f = ops.mlp_bwd(d_raw_f, fg_pts, views, sf, wb_f, save_f, pd=3, planes=pl_f, maxima=mx_f,
+                                                  guard=ctx.guards.get("nerfpp_fg_bwd"))
+        grads_b, d_pts_b, d_views_b = ops.mlp_bwd(d_raw_b, bg_pts, views, sb, wb_b, save_b, pd=4, planes=pl_b, maxima=mx_b,
+                                                  guard=ctx.guards.get("nerfpp_bg_bwd"))
         flat_gf = ops.nerf_wgrad(save_f, grads_f, d_raw_f, n * sf, pd=3, maxima=mx_f)
         flat_gb = ops.nerf_wgrad(save_b, grads_b, d_raw_b, n * sb, pd=4, maxima=mx_b)
         g_o, g_d = torch.empty_like(o), torch.empty_like(d)

@@ -284,6 +284,124 @@ def mlp_arithmetic(mode: Optional[str] = None) -> str:
     return _MLP_ARITHMETIC[0]
 
 
+RESIDENT_GUARDS = ("off", "fallback", "report", "strict")
+# Off by default: on the headline step the fallback mode costs 1.4 - 1.5 % (medians of alternating runs in both orders,
+# profiles/r07_resident_guard.txt) -- over the half per cent a default may cost.
+_RESIDENT_GUARD = [os.environ.get("SCNERF_RESIDENT_GUARD", "off")]
+if _RESIDENT_GUARD[0] not in RESIDENT_GUARDS:
+    raise ValueError("SCNERF_RESIDENT_GUARD must be one of %s, not %r" % ("|".join(RESIDENT_GUARDS), _RESIDENT_GUARD[0]))
+
+
+def resident_guard(mode: Optional[str] = None) -> str:
+    """The run-time check of the resident arithmetic's per-sample scales (csrc/resident_guard.h): every layer output
+    cut at a bound-derived scale S is checked for m = exponent(max|z|) + exponent(S) in [-3, 13), where the cut is fp32
+    grade.  "fallback" -- the resident kernels flag the 128-sample blocks holding a sample outside, and the
+    exact-fp32 kernels run those blocks again on the device (gated launches, no host synchronisation): a flagged block's
+    outputs are the fp32 arithmetic's bit for bit, every other block's are unchanged; "report" -- the same, plus per-layer
+    minimum margins and trip counts (resident_margins()); "strict" -- the margins, and a pass with a tripped sample raises
+    ResidentRangeError instead of running again (one host read per pass: for debugging); "off" (the default) -- the
+    launches without the check.  Without an argument: the mode in force.  Environment preset: SCNERF_RESIDENT_GUARD."""
+    if mode is not None:
+        if mode not in RESIDENT_GUARDS:
+            raise ValueError("resident_guard is one of " + ", ".join(RESIDENT_GUARDS))
+        _RESIDENT_GUARD[0] = mode
+    return _RESIDENT_GUARD[0]
+
+
+class ResidentRangeError(RuntimeError):
+    """A resident pass cut a layer output at a scale outside the range where the arithmetic is fp32 grade."""
+
+
+GUARD_LAYERS = tuple("layer_%d" % l for l in range(8)) + ("feature", "views")
+GUARD_SLOTS, GUARD_BIAS, GUARD_RANGE = 64, 256, (-3, 13)         # csrc/resident_guard.h
+GUARD_REPORT_FLOATS = len(GUARD_LAYERS) * (GUARD_SLOTS + 2)
+_GUARD_LAST = {}
+
+
+class GuardRecord:
+    """What one guarded resident launch leaves (csrc/resident_guard.h): int flags [ceil(P / 128)], the `any` word and, in
+    "report" / "strict", the report (per layer the largest 256 - m over 64 slots, then the samples under / over).  Views
+    of the one buffer guard_records() allocates; read only when asked."""
+    __slots__ = ("name", "blocks", "flags", "any", "report", "mode")
+
+    def __init__(self, name, blocks, flags, any_, report, mode):
+        self.name, self.blocks, self.flags, self.any, self.report, self.mode = name, blocks, flags, any_, report, mode
+
+    @property
+    def rerun(self) -> bool:
+        return self.mode in ("fallback", "report")
+
+    def args(self):
+        return _p(self.flags) if self.blocks else _p(self.any), _p(self.any), _p(self.report)
+
+    def margins(self) -> dict:
+        """{"reran_blocks": n, "blocks": N} and, with a report, {layer: {"min_log2": m or None (no live sample),
+        "under": k, "over": k}}"""
+        out = {"reran_blocks": int((self.flags != 0).sum()) if self.rerun else 0, "blocks": self.blocks}
+        if self.report is not None:
+            rep = self.report.cpu()
+            nl = len(GUARD_LAYERS)
+            best = rep[:nl * GUARD_SLOTS].view(nl, GUARD_SLOTS).max(1)[0]
+            counts = rep[nl * GUARD_SLOTS:].view(nl, 2)
+            for i, name in enumerate(GUARD_LAYERS):
+                out[name] = {"min_log2": GUARD_BIAS - int(best[i]) if best[i] > 0 else None,
+                             "under": int(counts[i, 0]), "over": int(counts[i, 1])}
+        return out
+
+    def raise_if_tripped(self):
+        if int(self.any.item()) == 0:
+            return
+        m = self.margins()
+        lo, hi = GUARD_RANGE
+        bad = [(n, m[n]) for n in GUARD_LAYERS if m[n]["under"] or m[n]["over"]]
+        raise ResidentRangeError("resident pass %r: %s outside [%d, %d) (%d of %d blocks)" % (
+            self.name, ", ".join("%s at min_log2 %s (%d under, %d over)" % (n, r["min_log2"], r["under"], r["over"]) for n, r in bad),
+            lo, hi, int((self.flags != 0).sum()), m["blocks"]))
+
+
+def guard_records(device, passes) -> dict:
+    """Records for the network passes of one call in the guard mode in force, carved from ONE zero-filled buffer:
+    passes = [(name, P), ...] -> {name: forward record, name + "_bwd": data-gradient record} ({} when "off").  The
+    data-gradient record shares its pass's block flags: a block the forward ran again in fp32 runs again in the data
+    gradients too.  resident_margins() reads the latest launched record of every pass."""
+    mode = _RESIDENT_GUARD[0]
+    if mode == "off":
+        return {}
+    rep = GUARD_REPORT_FLOATS if mode in ("report", "strict") else 0
+    layout, total = [], 0
+    for name, P in passes:
+        nb = (int(P) + 127) // 128
+        layout.append((name, nb, total))
+        total += nb + 2 + 2 * rep
+    buf = torch.zeros(total, dtype=torch.float32, device=device)
+    ints = buf.view(torch.int32)
+    out = {}
+    for name, nb, o in layout:
+        flags = ints[o:o + nb]
+        r = o + nb + 2
+        out[name] = GuardRecord(name, nb, flags, ints[o + nb:o + nb + 1], buf[r:r + rep] if rep else None, mode)
+        out[name + "_bwd"] = GuardRecord(name + "_bwd", nb, flags, ints[o + nb + 1:o + nb + 2],
+                                         buf[r + rep:r + 2 * rep] if rep else None, mode)
+    return out
+
+
+def resident_margins() -> dict:
+    """{pass: GuardRecord.margins()} of the latest guarded launch of every pass (reads the device)."""
+    return {name: rec.margins() for name, rec in _GUARD_LAST.items()}
+
+
+def _guard_after(guard: Optional[GuardRecord], rerun):
+    """after a guarded resident launch: strict -- raise on a trip; fallback / report -- rerun(flags, max_workgroups)
+    enqueues the gated exact-fp32 launch"""
+    if guard is None:
+        return
+    _GUARD_LAST[guard.name] = guard
+    if guard.mode == "strict":
+        guard.raise_if_tripped()
+    elif guard.rerun and guard.blocks:
+        rerun(_p(guard.flags), 0)
+
+
 def pack_for_arithmetic(flat_params: Tensor, train: bool, pd: int = 3, remap=None):
     """What mlp_fwd / coarse_stage_fwd / mlp_bwd take as `planes` in the arithmetic in force: the ResidentWeights
     ("resident") or None ("fp32": the fused fp32-MFMA kernels read the packed fp32 tables only)."""
@@ -419,9 +537,10 @@ _MAC_PER_SAMPLE = {3: 593408, 4: 593408 + 2 * 256 * 21}       # layer 0 and the 
 
 def mlp_fwd(pts: Tensor, viewdirs: Tensor, samples_per_ray: int, wpacked: Tensor,
             save: Optional[Tensor] = None, pd: int = 3, planes: Optional[Tensor] = None,
-            maxima: Optional["ChunkMaxima"] = None) -> Tensor:
+            maxima: Optional["ChunkMaxima"] = None, guard: Optional[GuardRecord] = None) -> Tensor:
     """pts [P, pd] (pd = 3: x y z; pd = 4: x y z 1/r) -> raw [P, 4] (rgb logits, sigma pre-activation).
-    `planes`: the ResidentWeights (pack_resident) -> the resident kernel; None -> the fused fp32-MFMA kernel."""
+    `planes`: the ResidentWeights (pack_resident) -> the resident kernel; None -> the fused fp32-MFMA kernel.
+    `guard`: a GuardRecord (guard_records) for the resident kernel's scale guard; None: no check."""
     _f(pts, "pts"), _f(wpacked, "wpacked")
     vptr, vstride = _vd(viewdirs)
     lay = ML.layout(pd)
@@ -435,7 +554,7 @@ def mlp_fwd(pts: Tensor, viewdirs: Tensor, samples_per_ray: int, wpacked: Tensor
     if isinstance(planes, ResidentWeights):
         if planes.pd != pd:
             raise ValueError("resident weights of another network variant")
-        return mlp_fwd_resident(pts, viewdirs, samples_per_ray, wpacked, planes, save, maxima)
+        return mlp_fwd_resident(pts, viewdirs, samples_per_ray, wpacked, planes, save, maxima, guard)
     raw = torch.empty((P, 4), dtype=torch.float32, device=pts.device)
     tag = "" if pd == 3 else "/pd4"
     if planes is not None:
@@ -449,7 +568,8 @@ def mlp_fwd(pts: Tensor, viewdirs: Tensor, samples_per_ray: int, wpacked: Tensor
 
 
 def mlp_fwd_resident(pts: Tensor, viewdirs: Tensor, samples_per_ray: int, wpacked: Tensor, rw: ResidentWeights,
-                     save: Optional[Tensor] = None, maxima: Optional[ChunkMaxima] = None) -> Tensor:
+                     save: Optional[Tensor] = None, maxima: Optional[ChunkMaxima] = None,
+                     guard: Optional[GuardRecord] = None) -> Tensor:
     """mlp_fwd in the resident arithmetic: one launch, three fp16 products per product, activations register-resident
     (csrc/mlp_fwd_h3.hip); save (training) receives the same workspace as mlp_fwd's."""
     _f(pts, "pts"), _f(wpacked, "wpacked")
@@ -467,10 +587,18 @@ def mlp_fwd_resident(pts: Tensor, viewdirs: Tensor, samples_per_ray: int, wpacke
     with PROFILE.region("mlp_fwd_h3_kernel%s/P=%d/%s" % ("" if pd == 3 else "/pd4", P, "train" if save is not None else "infer"),
                         2 * _MAC_PER_SAMPLE[pd] * P):
         mx = maxima if save is not None else None
-        st = _capi.load().scnerf_mlp_fwd_h3(pd, _p(pts), vptr, vstride, int(samples_per_ray), _p(wpacked), _p(rw.fwd),
-                                            _p(rw.scales), _p(raw), _p(save), P, _p(mx.x) if mx else None,
-                                            mx.chunks if mx else 0, mx.chunk_samples if mx else 0, _stream())
+        args = (pd, _p(pts), vptr, vstride, int(samples_per_ray), _p(wpacked), _p(rw.fwd), _p(rw.scales), _p(raw), _p(save), P,
+                _p(mx.x) if mx else None, mx.chunks if mx else 0, mx.chunk_samples if mx else 0)
+        if guard is None:
+            st = _capi.load().scnerf_mlp_fwd_h3(*args, _stream())
+        else:
+            st = _capi.load().scnerf_mlp_fwd_h3_guarded(*args, *guard.args(), _stream())
     _capi.check(st, "scnerf_mlp_fwd_h3")
+
+    def rerun(flags, wgs):
+        _capi.check(_capi.load().scnerf_mlp_fwd_gated(pd, _p(pts), vptr, vstride, int(samples_per_ray), _p(wpacked), _p(raw),
+                                                      _p(save), P, flags, wgs, _stream()), "scnerf_mlp_fwd_gated")
+    _guard_after(guard, rerun)
     return raw
 
 
@@ -479,7 +607,7 @@ COARSE_STAGE_SAMPLES = 64        # the fused coarse stage exists for two wave ti
 
 def coarse_stage_fwd(rays: Tensor, t_vals: Tensor, t_rand: Optional[Tensor], lindisp: bool, wpacked: Tensor,
                      save: Optional[Tensor], noise: Optional[Tensor], white_bkgd: bool, planes: Optional[Tensor] = None,
-                     maxima: Optional["ChunkMaxima"] = None):
+                     maxima: Optional["ChunkMaxima"] = None, guard: Optional[GuardRecord] = None):
     """coarse_sample + mlp_fwd + composite_fwd of the coarse stage as one launch (64 samples per ray):
     -> (z [n,64], pts [n,64,3], raw [n,64,4], rgb [n,3], disp [n], acc [n], weights [n,64], depth [n])."""
     _f(rays, "rays"), _f(t_vals, "t_vals"), _f(wpacked, "wpacked")
@@ -509,12 +637,22 @@ def coarse_stage_fwd(rays: Tensor, t_vals: Tensor, t_rand: Optional[Tensor], lin
             raise ValueError("the coarse stage samples 3-D points")
         with PROFILE.region("mlp_fwd_h3_kernel<coarse stage>/P=%d/%s" % (P, "train" if save is not None else "infer"),
                             2 * _MAC_PER_SAMPLE[3] * P):
-            st = _capi.load().scnerf_coarse_stage_fwd_h3(
-                _p(rays), rays.shape[1], _p(t_vals), _p(t_rand), int(bool(lindisp)), _p(wpacked), _p(planes.fwd),
-                _p(planes.scales), _p(save), _p(noise), int(bool(white_bkgd)), _p(z), _p(pts), _p(raw), _p(rgb), _p(disp),
-                _p(acc), _p(depth), _p(w), n, s, _p(maxima.x) if (maxima and save is not None) else None,
-                maxima.chunks if maxima else 0, maxima.chunk_samples if maxima else 0, _stream())
+            args = (_p(rays), rays.shape[1], _p(t_vals), _p(t_rand), int(bool(lindisp)), _p(wpacked), _p(planes.fwd),
+                    _p(planes.scales), _p(save), _p(noise), int(bool(white_bkgd)), _p(z), _p(pts), _p(raw), _p(rgb), _p(disp),
+                    _p(acc), _p(depth), _p(w), n, s, _p(maxima.x) if (maxima and save is not None) else None,
+                    maxima.chunks if maxima else 0, maxima.chunk_samples if maxima else 0)
+            if guard is None:
+                st = _capi.load().scnerf_coarse_stage_fwd_h3(*args, _stream())
+            else:
+                st = _capi.load().scnerf_coarse_stage_fwd_h3_guarded(*args, *guard.args(), _stream())
         _capi.check(st, "scnerf_coarse_stage_fwd_h3")
+
+        def rerun(flags, wgs):
+            _capi.check(_capi.load().scnerf_coarse_stage_fwd_gated(
+                _p(rays), rays.shape[1], _p(t_vals), _p(t_rand), int(bool(lindisp)), _p(wpacked), _p(save), _p(noise),
+                int(bool(white_bkgd)), _p(z), _p(pts), _p(raw), _p(rgb), _p(disp), _p(acc), _p(depth), _p(w), n, s, flags, wgs,
+                _stream()), "scnerf_coarse_stage_fwd_gated")
+        _guard_after(guard, rerun)
         return z, pts, raw, rgb, disp, acc, w, depth
     if planes is not None:
         raise TypeError("planes must be a ResidentWeights or None")
@@ -598,13 +736,13 @@ def save_workspace(P: int, device, pd: int = 3) -> Tensor:
 
 def mlp_bwd(d_raw: Tensor, pts: Tensor, viewdirs: Tensor, samples_per_ray: int, wpacked_bwd: Tensor,
             save: Tensor, pd: int = 3, planes: Optional[Tensor] = None, maxima: Optional["ChunkMaxima"] = None,
-            input_grad: bool = True):
-    """-> (grads workspace, d_pts [P,pd], d_views [P,3]).  `planes`: as mlp_fwd.  input_grad=False: d_pts / d_views
+            input_grad: bool = True, guard: Optional[GuardRecord] = None):
+    """-> (grads workspace, d_pts [P,pd], d_views [P,3]).  `planes`, `guard`: as mlp_fwd.  input_grad=False: d_pts / d_views
     are not needed -- the resident kernel skips them and returns None for both (the fp32 kernel computes them anyway)."""
     if isinstance(planes, ResidentWeights):
         if planes.pd != pd:
             raise ValueError("resident weights of another network variant")
-        return mlp_bwd_resident(d_raw, pts, viewdirs, samples_per_ray, wpacked_bwd, planes, save, maxima, input_grad)
+        return mlp_bwd_resident(d_raw, pts, viewdirs, samples_per_ray, wpacked_bwd, planes, save, maxima, input_grad, guard)
     _f(d_raw, "d_raw"), _f(pts, "pts"), _f(wpacked_bwd, "wpacked_bwd"), _f(save, "save")
     vptr, vstride = _vd(viewdirs)
     lay = ML.layout(pd)
@@ -625,7 +763,8 @@ def mlp_bwd(d_raw: Tensor, pts: Tensor, viewdirs: Tensor, samples_per_ray: int, 
 
 
 def mlp_bwd_resident(d_raw: Tensor, pts: Tensor, viewdirs: Tensor, samples_per_ray: int, wpacked_bwd: Tensor,
-                     rw: ResidentWeights, save: Tensor, maxima: Optional[ChunkMaxima] = None, input_grad: bool = True):
+                     rw: ResidentWeights, save: Tensor, maxima: Optional[ChunkMaxima] = None, input_grad: bool = True,
+                     guard: Optional[GuardRecord] = None):
     """mlp_bwd in the resident arithmetic (csrc/mlp_bwd_h3.hip): one launch -> (grads workspace, d_pts, d_views);
     input_grad=False: the instantiation without the input gradient, d_pts = d_views = None."""
     _f(d_raw, "d_raw"), _f(pts, "pts"), _f(wpacked_bwd, "wpacked_bwd"), _f(save, "save")
@@ -642,11 +781,23 @@ def mlp_bwd_resident(d_raw: Tensor, pts: Tensor, viewdirs: Tensor, samples_per_r
     with PROFILE.region("mlp_bwd_h3_kernel%s/P=%d" % ("" if pd == 3 else "/pd4", P), 2 * _MAC_PER_SAMPLE[pd] * P):
         if maxima is not None:
             maxima.scales = rw.scales
-        st = _capi.load().scnerf_mlp_bwd_h3(pd, _p(d_raw), _p(pts), vptr, vstride, int(samples_per_ray), _p(wpacked_bwd),
-                                            _p(rw.bwd), _p(rw.scales), _p(save), _p(grads), _p(d_pts), _p(d_views), P,
-                                            _p(maxima.z) if maxima else None, maxima.chunks if maxima else 0,
-                                            maxima.chunk_samples if maxima else 0, _stream())
+        args = (pd, _p(d_raw), _p(pts), vptr, vstride, int(samples_per_ray), _p(wpacked_bwd), _p(rw.bwd), _p(rw.scales),
+                _p(save), _p(grads), _p(d_pts), _p(d_views), P, _p(maxima.z) if maxima else None,
+                maxima.chunks if maxima else 0, maxima.chunk_samples if maxima else 0)
+        if guard is None:
+            st = _capi.load().scnerf_mlp_bwd_h3(*args, _stream())
+        else:
+            st = _capi.load().scnerf_mlp_bwd_h3_guarded(*args, *guard.args(), _stream())
     _capi.check(st, "scnerf_mlp_bwd_h3")
+
+    def rerun(flags, wgs):
+        # (the fp32 kernel always forms the input gradient: scratch when the caller does not want it)
+        dp = d_pts if input_grad else torch.empty((P, pd), dtype=torch.float32, device=dev)
+        dv = d_views if input_grad else torch.empty((P, 3), dtype=torch.float32, device=dev)
+        _capi.check(_capi.load().scnerf_mlp_bwd_gated(pd, _p(d_raw), _p(pts), vptr, vstride, int(samples_per_ray),
+                                                      _p(wpacked_bwd), _p(save), _p(grads), _p(dp), _p(dv), P, flags, wgs,
+                                                      _stream()), "scnerf_mlp_bwd_gated")
+    _guard_after(guard, rerun)
     return grads, d_pts, d_views
 
 
