@@ -231,11 +231,16 @@ def _kernel_gates(save, P, pd=3):
     return [torch.from_numpy(_gates_from_masks(masks[l], P, 8 if l < 8 else 4)) for l in range(9)]
 
 
-@pytest.mark.parametrize("n,kind,mode", [(256, "xavier", None), (4096, "xavier", None), (4096, "trained", None), (4096, "trained", "fp32")],
-                         ids=["256rays", "4096rays", "4096rays_trained", "4096rays_trained_fp32_yardstick"])
-def test_training_gradients_with_both_discontinuities_aligned(R, n, kind, mode):
+@pytest.mark.parametrize("n,kind,mode,data_rays", [(256, "xavier", None, False), (4096, "xavier", None, False),
+                                                   (4096, "trained", None, False), (4096, "trained", "fp32", False),
+                                                   (256, "xavier", None, True), (4096, "trained", None, True)],
+                         ids=["256rays", "4096rays", "4096rays_trained", "4096rays_trained_fp32_yardstick",
+                              "256rays_data_rays", "4096rays_trained_data_rays"])
+def test_training_gradients_with_both_discontinuities_aligned(R, n, kind, mode, data_rays):
     """(`kind`: the networks' weights -- the reference's initialisation, or both networks after 5000 training steps;
-    `mode`: None = the arithmetic in force, "fp32" = the exact-fp32 MFMA kernels as the yardstick on the same case.)
+    `mode`: None = the arithmetic in force, "fp32" = the exact-fp32 MFMA kernels as the yardstick on the same case;
+    `data_rays`: the GPU run's ray batch requires no gradient -- the benchmark's headline step: the data-gradient kernel
+    without the input gradient, composite_bwd without d rays_d, no ray reduction -- and there is no ray gradient to compare.)
     The golden cases bound the gradients behind the hierarchical sampler only loosely: one sample the reference
     algorithm places discontinuously (render.py:444, :455-456) or one ReLU whose pre-activation is a rounding from
     zero shifts every entry of a weight gradient a little at 24 rays.  Here both discontinuities are taken out of the
@@ -251,20 +256,20 @@ def test_training_gradients_with_both_discontinuities_aligned(R, n, kind, mode):
         R["ops"].mlp_arithmetic(mode)
         R["ops"].wgrad_arithmetic(mode)
     try:
-        _aligned_gradients_case(R, n, kind, mode, host_linspace)
+        _aligned_gradients_case(R, n, kind, mode, host_linspace, data_rays)
     finally:
         R["ops"].mlp_arithmetic(saved[0])
         R["ops"].wgrad_arithmetic(saved[1])
 
 
-def _aligned_gradients_case(R, n, kind, mode, host_linspace):
+def _aligned_gradients_case(R, n, kind, mode, host_linspace, data_rays=False):
     sc, sf = 64, 128                       # (4096 rays: the headline batch -- 8.6e8 ReLU decisions taken from the bit masks)
     net_c, net_f = make_net(R, 0, kind), make_net(R, 1, kind)
     rays = synth.ray_batch(n, seed=11)
     rnd = synth.render_randoms(n, sc, sf, seed=12)
     rnd_d = {k: v.cuda() for k, v in rnd.items()}
     target = torch.rand(n, 3, generator=torch.Generator().manual_seed(13))
-    rays_d = rays.cuda().requires_grad_(True)
+    rays_d = rays.cuda().requires_grad_(not data_rays)
     ret = R["render"].render_rays(rays_d, net_c, make_query(R), sc, retraw=True, perturb=1.0, N_importance=sf,
                                   network_fine=net_f, raw_noise_std=1.0, _randoms=rnd_d)
     node = _render_node(ret["rgb_map"])
@@ -300,21 +305,29 @@ def _aligned_gradients_case(R, n, kind, mode, host_linspace):
             e = np.abs(prm.grad.cpu().numpy() - ref).reshape(-1) / (np.abs(ref).max() + 1e-30)
             # (the 99.9 % quantile of a tensor with fewer than 2000 entries IS its largest entries: only the max bound applies)
             rep[tag + "/" + pn] = [float(np.quantile(e, 0.999)) if e.size >= 2000 else 0.0, float(e.max())]
-    cols = [0, 1, 2, 3, 4, 5, 8, 9, 10]
-    ge = np.abs(rays_d.grad[:, cols].cpu().numpy() - rays_o.grad[:, cols].numpy()).max(1) / np.abs(rays_o.grad.numpy()).max()
     worst = max(rep, key=lambda k_: rep[k_][1])
-    REPORT["training_gradients_discontinuities_aligned_%dx(64+128)%s%s" % (n, "" if kind == "xavier" else "_%s_weights" % kind,
-                                                                          "" if mode is None else "/" + mode)] = dict(
-        relu_decisions=n_gates, relu_decisions_differing_from_the_oracles_own=flips,
-        worst_q999=max(v[0] for v in rep.values()), worst_max=rep[worst][1], worst_parameter=worst,
-        d_ray_batch_worst_ray=float(ge.max()))
+    entry = dict(relu_decisions=n_gates, relu_decisions_differing_from_the_oracles_own=flips,
+                 worst_q999=max(v[0] for v in rep.values()), worst_max=rep[worst][1], worst_parameter=worst)
+    if data_rays:
+        assert rays_d.grad is None
+    else:
+        cols = [0, 1, 2, 3, 4, 5, 8, 9, 10]
+        ge = np.abs(rays_d.grad[:, cols].cpu().numpy() - rays_o.grad[:, cols].numpy()).max(1) / np.abs(rays_o.grad.numpy()).max()
+        entry["d_ray_batch_worst_ray"] = float(ge.max())
+    REPORT["training_gradients_discontinuities_aligned_%dx(64+128)%s%s%s" % (
+        n, "" if kind == "xavier" else "_%s_weights" % kind, "" if mode is None else "/" + mode,
+        "_data_rays" if data_rays else "")] = entry
     for key, (q999, mx) in rep.items():
         assert q999 <= 2e-5 and mx <= 1e-4, (key, q999, mx)
-    assert ge.max() <= 1e-4, float(ge.max())
+    if not data_rays:
+        assert ge.max() <= 1e-4, float(ge.max())
 
 
-def test_training_step_is_bit_reproducible(R, arithmetic):
-    """The same 4096-ray training step five times: every output, the ray gradients and every parameter gradient of both
+@pytest.mark.parametrize("rays_need_grad", [True, False], ids=["differentiable_rays", "data_rays"])
+def test_training_step_is_bit_reproducible(R, arithmetic, rays_need_grad):
+    """(`rays_need_grad` False: the ray batch is data -- the data-gradient kernel without the input gradient, whose schedule
+    passes over three products and runs their epilogues unfilled: the argument below applies to it at least as much.)
+    The same 4096-ray training step five times: every output, the ray gradients and every parameter gradient of both
     networks bit for bit the same.  All sums of the path run in a fixed order (per-GEMM partial slabs reduced by index,
     fp64 prefix products, maxima through integer atomicMax), so anything else is a race -- and the LDS schedules of the
     resident kernels and the weight-gradient GEMMs (two slab images, one barrier per slab; chunk rings behind one
@@ -327,11 +340,11 @@ def test_training_step_is_bit_reproducible(R, arithmetic):
     params = list(net_c.parameters()) + list(net_f.parameters())
 
     def once():
-        r = rays.clone().requires_grad_(True)
+        r = rays.clone().requires_grad_(rays_need_grad)
         ret = R["render"].render_rays(r, net_c, make_query(R), sc, retraw=True, perturb=1.0, N_importance=sf,
                                       network_fine=net_f, raw_noise_std=1.0, _randoms=rnd)
         loss = torch.mean((ret["rgb_map"] - target) ** 2) + torch.mean((ret["rgb0"] - target) ** 2)
-        grads = torch.autograd.grad(loss, [r] + params)
+        grads = torch.autograd.grad(loss, ([r] if rays_need_grad else []) + params)
         keys = ("rgb_map", "disp_map", "acc_map", "raw", "rgb0", "disp0", "acc0", "z_std")
         return [ret[k].detach().clone() for k in keys] + [g.detach().clone() for g in grads]
 
