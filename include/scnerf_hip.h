@@ -404,6 +404,24 @@ int scnerf_mlp_bwd_gated(int pt_dims, const float* d_raw, const float* pts, cons
                          int samples_per_ray, const float* wpacked_bwd, const float* save, float* grads, float* d_pts,
                          float* d_views, long long n_samples, const int* flags, int max_workgroups, void* stream);
 
+/* Forward-only passes on ONE fp16 product per product (opt-in: ops.inference_arithmetic("fast")): scnerf_mlp_fwd_h3 (run_network +
+ * Embedder + NeRF.forward, NeRF/create_nerf.py:18-32, NeRF/run_nerf_helpers.py:24-72, :105-128, as called without
+ * gradients by render_path, NeRF/render.py:143-183, and render_single_image, nerfplusplus/ddp_train_nerf.py:135-170) and scnerf_coarse_stage_fwd_h3 (NeRF/render.py:235-262) with only the
+ * (Wh Xh) MFMA of every product: operands rounded to fp16 after their power-of-two scale, fp32 accumulation -- a relative
+ * error near 2^-11 per operand instead of 2^-22, a third of the matrix instructions.  Same streams, scale table, biases,
+ * ReLU and per-sample scale rule as the entries they are named after; the argument lists are theirs without `save`
+ * (there is no training instantiation).  chunk_amax / n_chunks / chunk_samples are accepted and not used, as in those
+ * entries with save == NULL; there is no guard record: the guard's range is a statement about the low plane. */
+int scnerf_mlp_fwd_h3_fast(int pt_dims, const float* pts, const float* viewdirs, int vd_stride, int samples_per_ray,
+                           const float* wpacked, const short* stream_fwd, const float* scales, float* raw,
+                           long long n_samples, float* chunk_amax, int n_chunks, long long chunk_samples, void* stream);
+int scnerf_coarse_stage_fwd_h3_fast(const float* rays, int ray_stride, const float* t_vals, const float* t_rand,
+                                    int lindisp, const float* wpacked, const short* stream_fwd, const float* scales,
+                                    const float* noise, int white_bkgd, float* z, float* pts, float* raw,
+                                    float* rgb_map, float* disp_map, float* acc_map, float* depth_map, float* weights,
+                                    int n_rays, int n_samples, float* chunk_amax, int n_chunks, long long chunk_samples,
+                                    void* stream);
+
 /* ------------------------------------------------------------------ PRD loss --------- */
 
 /* Projected-ray-distance loss, proj_ray_dist_loss_single (model/ray_dist_loss.py:22-246) after its

@@ -83,6 +83,8 @@ PROTOTYPES = {
                                            P, P, P, P],
     "scnerf_fine_stage_fwd_h3_guarded": [P, I, P, P, P, I, P, P, P, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, P,
                                          I, LL, P, P, P, P],
+    "scnerf_mlp_fwd_h3_fast": [I, P, P, I, I, P, P, P, P, LL, P, I, LL, P],
+    "scnerf_coarse_stage_fwd_h3_fast": [P, I, P, P, I, P, P, P, P, I, P, P, P, P, P, P, P, P, I, I, P, I, LL, P],
     "scnerf_mlp_fwd_gated": [I, P, P, I, I, P, P, P, LL, P, I, P],
     "scnerf_coarse_stage_fwd_gated": [P, I, P, P, I, P, P, P, I, P, P, P, P, P, P, P, P, I, I, P, I, P],
     "scnerf_mlp_bwd_gated": [I, P, P, P, I, I, P, P, P, P, P, LL, P, I, P],

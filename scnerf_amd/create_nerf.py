@@ -44,7 +44,7 @@ class _QueryFunction(torch.autograd.Function):
         else:
             wf, planes = ops.inference_packs(net, flat)       # (forward-only: packed once per weight version)
         maxima = ops.ChunkMaxima(p.shape[0], p.device) if (train and isinstance(planes, ops.ResidentWeights)) else None
-        guards = ops.guard_records(p.device, [("query", p.shape[0])]) if isinstance(planes, ops.ResidentWeights) else {}
+        guards = ops.guard_records(p.device, [("query", p.shape[0])], fast=planes.fast) if isinstance(planes, ops.ResidentWeights) else {}
         raw = ops.mlp_fwd(p, v, spr, wf, save, planes=planes, maxima=maxima, guard=guards.get("query"))
         ctx.guard_bwd = guards.get("query_bwd")
         ctx.state = (p, v, spr, save, ops.pack_weights(flat, "bwd") if train else None, shape, viewdirs.shape, planes, maxima)

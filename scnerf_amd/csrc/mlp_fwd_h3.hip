@@ -209,6 +209,38 @@ extern "C" int scnerf_coarse_stage_fwd_h3(const float* rays, int ray_stride, con
                                               n_samples, chunk_amax, n_chunks, chunk_samples, nullptr, nullptr, nullptr, stream);
 }
 
+// ---- forward-only, one fp16 product per product (mlp_fwd_h3_kernel.h, PRODUCTS == 1) ----
+extern "C" int scnerf_mlp_fwd_h3_fast(int pt_dims, const float* pts, const float* viewdirs, int vd_stride, int samples_per_ray,
+                                      const float* wpacked, const short* stream_fwd, const float* scales, float* raw,
+                                      long long n_samples, float* chunk_amax, int n_chunks, long long chunk_samples,
+                                      void* stream) {
+    SCN_RETURN_IF(!pts || !viewdirs || !wpacked || !stream_fwd || !scales || !raw, SCN_EINVAL);
+    SCN_RETURN_IF(samples_per_ray < 1 || vd_stride < 3 || n_samples < 0 || (pt_dims != 3 && pt_dims != 4), SCN_EINVAL);
+    SCN_RETURN_IF(n_samples >= (1LL << 31), SCN_ENOSUP);       // (the kernels index samples with 31 bits)
+    SCN_RETURN_IF(chunk_amax && (n_chunks < 1 || chunk_samples < 32 || chunk_samples % 32), SCN_EINVAL);
+    if (n_samples == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    // (chunk_amax: maxima are left for the weight-gradient GEMMs, by training passes only)
+    return pt_dims == 3 ? scn::h3f::fwd_h3_pd3_fast(pts, viewdirs, vd_stride, samples_per_ray, wpacked, stream_fwd, scales, raw, n_samples, st)
+                        : scn::h3f::fwd_h3_pd4_fast(pts, viewdirs, vd_stride, samples_per_ray, wpacked, stream_fwd, scales, raw, n_samples, st);
+}
+
+extern "C" int scnerf_coarse_stage_fwd_h3_fast(const float* rays, int ray_stride, const float* t_vals, const float* t_rand,
+                                               int lindisp, const float* wpacked, const short* stream_fwd, const float* scales,
+                                               const float* noise, int white_bkgd, float* z, float* pts, float* raw,
+                                               float* rgb_map, float* disp_map, float* acc_map, float* depth_map, float* weights,
+                                               int n_rays, int n_samples, float* chunk_amax, int n_chunks,
+                                               long long chunk_samples, void* stream) {
+    SCN_RETURN_IF(!rays || !t_vals || !wpacked || !stream_fwd || !scales || !z || !pts || !raw || !rgb_map || !disp_map || !acc_map, SCN_EINVAL);
+    SCN_RETURN_IF(n_rays < 0 || ray_stride < 11, SCN_EINVAL);
+    SCN_RETURN_IF(n_samples != scn::h3f::kCoarseSamples || n_rays >= (1 << 25), SCN_ENOSUP);     // (31-bit sample indices)
+    SCN_RETURN_IF(chunk_amax && (n_chunks < 1 || chunk_samples < 32 || chunk_samples % 32), SCN_EINVAL);
+    if (n_rays == 0) return 0;
+    const scn::h3f::CoarseStage cs{rays, ray_stride, n_rays, t_vals, t_rand, lindisp, z, pts, noise, white_bkgd,
+                                   rgb_map, disp_map, acc_map, depth_map, weights};
+    return scn::h3f::fwd_h3_coarse_fast(cs, rays, ray_stride, wpacked, stream_fwd, scales, raw, (hipStream_t)stream);
+}
+
 extern "C" int scnerf_fine_stage_fwd_h3_guarded(const float* rays, int ray_stride, const float* z_c, const float* w_c,
                                                 const float* u, int u_row_stride, const float* wpacked, const short* stream_fwd,
                                                 const float* scales, float* save, const float* noise, int white_bkgd, float* z_f,

@@ -46,6 +46,14 @@ int fwd_h3_pd4(const float* pts, const float* viewdirs, int vd_stride, int sampl
 // the fused coarse stage (sampling + network + compositing)
 int fwd_h3_coarse(const CoarseStage& cs, const float* rays, int ray_stride, const float* wpacked, const short* stream_fwd,
                   const float* scales, float* raw, float* save, ChunkMaxima cm, hipStream_t st);
+// the same two, forward-only, on one fp16 product per product (mlp_fwd_h3_kernel.h PRODUCTS == 1): no workspace, no chunk
+// maxima, no guard record (mlp_fwd_h3_pd3_fast.hip, _pd4_fast.hip, _coarse_fast.hip)
+int fwd_h3_pd3_fast(const float* pts, const float* viewdirs, int vd_stride, int samples_per_ray, const float* wpacked,
+                    const short* stream_fwd, const float* scales, float* raw, long long n_samples, hipStream_t st);
+int fwd_h3_pd4_fast(const float* pts, const float* viewdirs, int vd_stride, int samples_per_ray, const float* wpacked,
+                    const short* stream_fwd, const float* scales, float* raw, long long n_samples, hipStream_t st);
+int fwd_h3_coarse_fast(const CoarseStage& cs, const float* rays, int ray_stride, const float* wpacked, const short* stream_fwd,
+                       const float* scales, float* raw, hipStream_t st);
 // the fused fine stage (sampler + merge + network + compositing); 64 + n_importance in {128, 192, 256}
 int fwd_h3_fine_train(const FineStage& fs, const float* wpacked, const short* stream_fwd, const float* scales, float* raw,
                       float* save, ChunkMaxima cm, hipStream_t st);

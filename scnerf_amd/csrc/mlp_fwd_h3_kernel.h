@@ -1,5 +1,6 @@
 // mlp_fwd_h3_kernel.h -- the resident-arithmetic forward kernel (see mlp_fwd_h3.hip for what it replaces) and its launch
-// templates.  Included by one translation unit per instantiation group (mlp_fwd_h3_pd3.hip, _pd4.hip, _coarse.hip): the
+// templates.  Included by one translation unit per instantiation group (mlp_fwd_h3_pd3.hip, _pd4.hip, _coarse.hip, the fine
+// stage's two, and the one-product groups _pd3_fast.hip, _pd4_fast.hip, _coarse_fast.hip): the
 // kernel is a long straight-line program, and compiled side by side its variants take a third of the wall time.
 #pragma once
 #include <scn_wave.h>
@@ -69,7 +70,8 @@ struct Density {
 template <bool ON> struct MaskBits { unsigned bits0, bits1, words[4]; };
 template <> struct MaskBits<false> {};
 
-template <bool TRAIN, int KIND>
+// PRODUCTS == 1: the cut leaves the high plane only (no residual; `ol` is never touched)
+template <bool TRAIN, int KIND, int PRODUCTS = 3>
 struct FwdEpi : std::conditional_t<KIND == 1, Density, NoDensity>, MaskBits<TRAIN && KIND != 2> {
     float os, s_next, am;
     const float* bias;         // LDS lane-vector table of the layer, + 4 h
@@ -90,7 +92,9 @@ struct FwdEpi : std::conditional_t<KIND == 1, Density, NoDensity>, MaskBits<TRAI
         if constexpr (lab::kNoEpilogue) {
             if constexpr (SUB == 1) {
                 oh[sl][c0] = __float_as_uint(acc[x][4 * q]) & 0x3bff3bffu; oh[sl][c0 + 1] = __float_as_uint(acc[x][4 * q + 1]) & 0x3bff3bffu;
-                ol[sl][c0] = __float_as_uint(acc[x][4 * q + 2]) & 0x3bff3bffu; ol[sl][c0 + 1] = __float_as_uint(acc[x][4 * q + 3]) & 0x3bff3bffu;
+                if constexpr (PRODUCTS == 3) {
+                    ol[sl][c0] = __float_as_uint(acc[x][4 * q + 2]) & 0x3bff3bffu; ol[sl][c0 + 1] = __float_as_uint(acc[x][4 * q + 3]) & 0x3bff3bffu;
+                }
             }
         } else if constexpr (SUB == 0) {
             bq = *reinterpret_cast<const f32x4*>(bias + (4 * T + q) * 8);
@@ -111,12 +115,12 @@ struct FwdEpi : std::conditional_t<KIND == 1, Density, NoDensity>, MaskBits<TRAI
             hp = pack_f16_scaled(v[0], v[1], s_next);
         } else if constexpr (SUB == 7) {
             oh[sl][c0] = hp;
-            ol[sl][c0] = pack_f16(residual_f16<0>(v[0], s_next, hp), residual_f16<1>(v[1], s_next, hp));
+            if constexpr (PRODUCTS == 3) ol[sl][c0] = pack_f16(residual_f16<0>(v[0], s_next, hp), residual_f16<1>(v[1], s_next, hp));
         } else if constexpr (SUB == 8) {
             hp = pack_f16_scaled(v[2], v[3], s_next);
         } else if constexpr (SUB == 9) {
             oh[sl][c0 + 1] = hp;
-            ol[sl][c0 + 1] = pack_f16(residual_f16<0>(v[2], s_next, hp), residual_f16<1>(v[3], s_next, hp));
+            if constexpr (PRODUCTS == 3) ol[sl][c0 + 1] = pack_f16(residual_f16<0>(v[2], s_next, hp), residual_f16<1>(v[3], s_next, hp));
         } else if constexpr (SUB == 10) {
             if constexpr (TRAIN && !lab::kNoStore) {
                 // (wave-uniform base + the lane's 32-bit offset: as 64-bit per-lane pointers the eight piece bases of a
@@ -162,15 +166,23 @@ struct FwdKernelArgs {
 };
 static_assert(sizeof(FwdKernelArgs) == 72 + sizeof(CoarseStage) + sizeof(FineStage) + sizeof(ChunkMaxima), "argument block layout");
 
-template <int PD, bool TRAIN, int STAGE>
+// PRODUCTS: fp16 products per product.  3: (Wh Xh) + (Wh Xl) + (Wl Xh), fp32 grade -- every training pass and the default
+// of every forward-only one.  1: (Wh Xh) alone, fp16-grade operands with fp32 accumulation, for forward-only passes that
+// opt in (ops.inference_arithmetic("fast")): same stream, same slot schedule, a third of the MFMAs; the cut forms no
+// residual, the low operand planes do not exist (128 registers lie idle) and the scale guard -- a statement about the
+// low plane's range -- does not apply.  Bias, ReLU, maxima and the per-sample scale rule are the same instructions.
+template <int PD, bool TRAIN, int STAGE, int PRODUCTS = 3>
 __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_h3_kernel(
     const float* __restrict__ pts, const float* __restrict__ viewdirs, int vd_stride, int samples_per_ray,
     const float* __restrict__ wpk, const short* __restrict__ wh3, const float* __restrict__ sc,
     float* __restrict__ raw, float* __restrict__ save_arg, long P, CoarseStage cs, FineStage fs, ChunkMaxima cm) {
     using V = Var<PD>;
     constexpr int ES = V::kES, NE = ES / 8;
-    constexpr bool COARSE = STAGE == kCoarse, FINE = STAGE == kFine;
+    constexpr bool COARSE = STAGE == kCoarse, FINE = STAGE == kFine, ONE = PRODUCTS == 1;
+    static_assert(!ONE || (!TRAIN && !FINE), "one product: forward-only, sample-list forward and coarse stage");
     claim_whole_register_file();
+    // the low plane of an operand: in the one-product arithmetic there is none (unit() does not read what it is given)
+    auto low_of = [](const u32x4& lo, const u32x4& hi) { if constexpr (ONE) return hi; else return lo; };
     float* const save = TRAIN ? save_arg : nullptr;
     const long Ppad_kernel = padded_samples(P);
 
@@ -291,7 +303,10 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_h3_kernel(
                                                     uniform(wave_id()), lane);
         const float s_e = scale_for(m_e);
 #pragma unroll
-        for (int u = 0; u < NE; ++u) cut8(e + 8 * u, s_e, eh[u], el[u]);
+        for (int u = 0; u < NE; ++u) {
+            if constexpr (ONE) cut8_high(e + 8 * u, s_e, eh[u]);
+            else cut8(e + 8 * u, s_e, eh[u], el[u]);
+        }
     }
     block_sync();                       // the first chunk and the tables are in LDS
     ring_prime(w);
@@ -322,13 +337,15 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_h3_kernel(
 
     // the scale guard (resident_guard.h): its record read from the argument block where it is used
     auto guard = [&](int guard_layer, float am, float s) __attribute__((always_inline)) {
-        const FwdKernelArgs mirror{pts, viewdirs, vd_stride, samples_per_ray, wpk, wh3, sc, raw, save_arg, P, cs, fs, cm};
-        const auto* late = late_args(mirror);
-        const ResidentGuard g{late->cm.guard.flags, late->cm.guard.any, late->cm.guard.report};
-        guard_check(g, guard_layer, am, s, lane_now().live, wave_tile);
+        if constexpr (!ONE) {          // (the one-product instantiations take no record)
+            const FwdKernelArgs mirror{pts, viewdirs, vd_stride, samples_per_ray, wpk, wh3, sc, raw, save_arg, P, cs, fs, cm};
+            const auto* late = late_args(mirror);
+            const ResidentGuard g{late->cm.guard.flags, late->cm.guard.any, late->cm.guard.report};
+            guard_check(g, guard_layer, am, s, lane_now().live, wave_tile);
+        }
     };
 
-    using Relu = FwdEpi<TRAIN, 0>;
+    using Relu = FwdEpi<TRAIN, 0, PRODUCTS>;
     auto make_relu = [&](int l, float s_in) {         // epilogue of trunk layer l whose input was cut at s_in
         Relu e;
         e.os = inv_pow2(s_in) * scale_of(l, kSwInv);
@@ -350,11 +367,11 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_h3_kernel(
     {
         auto operand = [&](auto s_tag, u32x4& xh, u32x4& xl) {
             constexpr int s = decltype(s_tag)::value;
-            xh = eh[s]; xl = el[s];
+            xh = eh[s]; xl = low_of(el[s], xh);
         };
         static_for<4>([&](auto p_tag) {
             constexpr int PP = decltype(p_tag)::value;
-            tile_pair<NE * PP, NE>(w, acc[PP & 1], operand, NoFill{});
+            tile_pair<NE * PP, NE, PRODUCTS>(w, acc[PP & 1], operand, NoFill{});
             if constexpr (PP < 3) epi_all<Relu, PP>(prev, acc[PP & 1], bh[0], bl[0]);
         });
     }
@@ -368,13 +385,13 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_h3_kernel(
         constexpr int NK = NEF + 16;
         auto operand = [&](auto s_tag, u32x4& xh, u32x4& xl) {
             constexpr int s = decltype(s_tag)::value;
-            if constexpr (s < NEF) { xh = eh[s]; xl = el[s]; }
-            else { xh = bh[X][s - NEF]; xl = bl[X][s - NEF]; }
+            if constexpr (s < NEF) { xh = eh[s]; xl = low_of(el[s], xh); }
+            else { xh = bh[X][s - NEF]; xl = low_of(bl[X][s - NEF], xh); }
         };
         using Pend = std::remove_reference_t<decltype(pend)>;
         using Cur = std::remove_reference_t<decltype(cur)>;
         // pair 0 under it: the pending pair (tiles 6, 7 of the input = slabs 12 .. 15: due before slot 6 (NEF + 12))
-        tile_pair<U0, NK>(w, acc[0], operand, [&](auto sg_tag) {
+        tile_pair<U0, NK, PRODUCTS>(w, acc[0], operand, [&](auto sg_tag) {
             epi_slot<Pend, 3, decltype(sg_tag)::value, NEF >= 4 ? 12 : 9>(pend, acc[1], bh[X], bl[X]);
         });
         if constexpr (std::is_base_of_v<MaskBits<true>, Pend>) store_mask(pend, pend_mask_sect);
@@ -385,13 +402,13 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_h3_kernel(
         guard(layer == kLayerFeat ? 7 : layer - 1, am_in, pend.s_next);
         const float am = fmaxf(am_in, am_floor);
         cur.s_next = scale_for(fmaxf(__builtin_fmaf(scale_of(layer, kBoundA), am, scale_of(layer, kBoundB)), bound_floor));
-        tile_pair<U0 + NK, NK>(w, acc[1], operand, [&](auto sg_tag) {
+        tile_pair<U0 + NK, NK, PRODUCTS>(w, acc[1], operand, [&](auto sg_tag) {
             epi_slot<Cur, 0, decltype(sg_tag)::value, 12>(cur, acc[0], bh[X ^ 1], bl[X ^ 1]);
         });
-        tile_pair<U0 + 2 * NK, NK>(w, acc[0], operand, [&](auto sg_tag) {
+        tile_pair<U0 + 2 * NK, NK, PRODUCTS>(w, acc[0], operand, [&](auto sg_tag) {
             epi_slot<Cur, 1, decltype(sg_tag)::value, 12>(cur, acc[1], bh[X ^ 1], bl[X ^ 1]);
         });
-        tile_pair<U0 + 3 * NK, NK>(w, acc[1], operand, [&](auto sg_tag) {
+        tile_pair<U0 + 3 * NK, NK, PRODUCTS>(w, acc[1], operand, [&](auto sg_tag) {
             epi_slot<Cur, 2, decltype(sg_tag)::value, 12>(cur, acc[0], bh[X ^ 1], bl[X ^ 1]);
         });
     };
@@ -413,7 +430,10 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_h3_kernel(
                 e[4 * g] = v[0]; e[4 * g + 1] = v[1]; e[4 * g + 2] = v[2]; e[4 * g + 3] = v[3];
             }
 #pragma unroll
-            for (int u = 0; u < NE; ++u) cut8(e + 8 * u, prev.s_next, eh[u], el[u]);
+            for (int u = 0; u < NE; ++u) {
+                if constexpr (ONE) cut8_high(e + 8 * u, prev.s_next, eh[u]);
+                else cut8(e + 8 * u, prev.s_next, eh[u], el[u]);
+            }
             trunk_layer(I<0>{}, I<NE>{}, I<0>{}, prev, cur, l - 1, l, m_e, 0.f);
         }
         prev = cur;
@@ -430,7 +450,7 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_h3_kernel(
         vx = viewdirs[ray * vd_stride + 0]; vy = viewdirs[ray * vd_stride + 1]; vz = viewdirs[ray * vd_stride + 2];
     }
     const float m_ev = fmaxf(fmaxf(1.f, fabsf(vx)), fmaxf(fabsf(vy), fabsf(vz)));
-    FwdEpi<TRAIN, 1> epi7;
+    FwdEpi<TRAIN, 1, PRODUCTS> epi7;
     {
         const Relu t = make_relu(7, prev.s_next);
         epi7.os = t.os; epi7.s_next = 1.f; epi7.am = 0.f; epi7.sg = 0.f; epi7.bias = t.bias;
@@ -438,7 +458,7 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_h3_kernel(
         epi7.prime();
     }
     trunk_layer(I<0>{}, I<0>{}, I<0>{}, prev, epi7, 6, 7, 0.f, 0.f);
-    FwdEpi<TRAIN, 2> epif;
+    FwdEpi<TRAIN, 2, PRODUCTS> epif;
     epif.os = inv_pow2(epi7.s_next) * scale_of(kLayerFeat, kSwInv);
     epif.s_next = 1.f; epif.am = 0.f;
     epif.bias = tab_h + kTabFeat;
@@ -461,8 +481,13 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_h3_kernel(
             store_pe_tile<3, 4, 16, 32>(w.lds + kStreamLds + kTableFloats * 4, save + (long)kSaveEviews * Ppad, wave_tile,
                                         uniform(wave_id()), (int)pinned_here((unsigned)lane_id()));
         }
-        cut8(ev, epif.s_next, vh[0], vl[0]);
-        cut8(ev + 8, epif.s_next, vh[1], vl[1]);
+        if constexpr (ONE) {
+            cut8_high(ev, epif.s_next, vh[0]);
+            cut8_high(ev + 8, epif.s_next, vh[1]);
+        } else {
+            cut8(ev, epif.s_next, vh[0], vl[0]);
+            cut8(ev + 8, epif.s_next, vh[1], vl[1]);
+        }
     }
     Relu epiv;
     epiv.os = inv_pow2(epif.s_next) * scale_of(kLayerViews, kSwInv);
@@ -475,17 +500,17 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_h3_kernel(
     {
         auto operand = [&](auto s_tag, u32x4& xh, u32x4& xl) {
             constexpr int s = decltype(s_tag)::value;
-            if constexpr (s < 16) { xh = bh[0][s]; xl = bl[0][s]; }
-            else { xh = vh[s - 16]; xl = vl[s - 16]; }
+            if constexpr (s < 16) { xh = bh[0][s]; xl = low_of(bl[0][s], xh); }
+            else { xh = vh[s - 16]; xl = low_of(vl[s - 16], xh); }
         };
-        tile_pair<0, 18>(w, acc[0], operand, [&](auto sg_tag) {
-            epi_slot<FwdEpi<TRAIN, 2>, 3, decltype(sg_tag)::value, 9>(epif, acc[1], bh[0], bl[0]);
+        tile_pair<0, 18, PRODUCTS>(w, acc[0], operand, [&](auto sg_tag) {
+            epi_slot<FwdEpi<TRAIN, 2, PRODUCTS>, 3, decltype(sg_tag)::value, 9>(epif, acc[1], bh[0], bl[0]);
         });
         const float am_f = amax_of(epif.am);
         guard(kLayerFeat, am_f, epif.s_next);
         const float am = fmaxf(am_f, m_ev);
         epiv.s_next = scale_for(__builtin_fmaf(scale_of(kLayerViews, kBoundA), am, scale_of(kLayerViews, kBoundB)));
-        tile_pair<18, 18>(w, acc[1], operand, [&](auto sg_tag) {
+        tile_pair<18, 18, PRODUCTS>(w, acc[1], operand, [&](auto sg_tag) {
             epi_slot<Relu, 0, decltype(sg_tag)::value, 12>(epiv, acc[0], bh[1], bl[1]);
         });
         epi_all<Relu, 1>(epiv, acc[1], bh[1], bl[1]);
@@ -495,9 +520,9 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_h3_kernel(
 
     // ---- rgb: one output tile over the 128 views-layer activations (stream units 36 .. 39) ----
     f32x16 accc[2];
-    tile_single<36, 4>(w, accc, [&](auto s_tag, u32x4& xh, u32x4& xl) {
+    tile_single<36, 4, PRODUCTS>(w, accc, [&](auto s_tag, u32x4& xh, u32x4& xl) {
         constexpr int s = decltype(s_tag)::value;
-        xh = bh[1][s]; xl = bl[1][s];
+        xh = bh[1][s]; xl = low_of(bl[1][s], xh);
     }, NoFill{});
     // (+ 0, or + NaN when a parameter of the network is not finite: mlp_fwd_h3.hip's scale pass)
     const float os_rgb = __builtin_fmaf(inv_pow2(epiv.s_next), scale_of(kLayerRgb, kSwInv), scale_of(kLayerRgb, kPoison));
@@ -566,26 +591,26 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_h3_kernel(
 }
 
 
-template <int PD, bool TRAIN>
+template <int PD, bool TRAIN, int PRODUCTS = 3>
 inline int launch_fwd_h3(const float* pts, const float* viewdirs, int vd_stride, int samples_per_ray, const float* wpacked,
                          const short* wh3, const float* scales, float* raw, float* save, long long n_samples, ChunkMaxima cm,
                          hipStream_t st) {
     constexpr unsigned lds = fwd_lds_bytes<PD>();
-    SCN_LDS_OPT_IN((mlp_fwd_h3_kernel<PD, TRAIN, kPoints>), lds);
-    hipLaunchKernelGGL((mlp_fwd_h3_kernel<PD, TRAIN, kPoints>), dim3(scn_ceil_div(n_samples, kSamplesPerBlock)), dim3(kThreads),
+    SCN_LDS_OPT_IN((mlp_fwd_h3_kernel<PD, TRAIN, kPoints, PRODUCTS>), lds);
+    hipLaunchKernelGGL((mlp_fwd_h3_kernel<PD, TRAIN, kPoints, PRODUCTS>), dim3(scn_ceil_div(n_samples, kSamplesPerBlock)), dim3(kThreads),
                        lds, st, pts, viewdirs, vd_stride, samples_per_ray, wpacked, wh3, scales, raw, save, (long)n_samples,
                        CoarseStage{}, FineStage{}, cm);
     return scn_launch_status();
 }
 
 
-template <bool TRAIN>
+template <bool TRAIN, int PRODUCTS = 3>
 inline int launch_coarse_h3(const CoarseStage& cs, const float* rays, int ray_stride, const float* wpacked, const short* stream_fwd,
                             const float* scales, float* raw, float* save, ChunkMaxima cm, hipStream_t st) {
     constexpr unsigned lds = fwd_lds_bytes<3>();
     const long P = (long)cs.n_rays * kCoarseSamples;
-    SCN_LDS_OPT_IN((mlp_fwd_h3_kernel<3, TRAIN, kCoarse>), lds);
-    hipLaunchKernelGGL((mlp_fwd_h3_kernel<3, TRAIN, kCoarse>), dim3(scn_ceil_div(P, kSamplesPerBlock)), dim3(kThreads), lds, st,
+    SCN_LDS_OPT_IN((mlp_fwd_h3_kernel<3, TRAIN, kCoarse, PRODUCTS>), lds);
+    hipLaunchKernelGGL((mlp_fwd_h3_kernel<3, TRAIN, kCoarse, PRODUCTS>), dim3(scn_ceil_div(P, kSamplesPerBlock)), dim3(kThreads), lds, st,
                        (const float*)nullptr, rays + 8, ray_stride, kCoarseSamples, wpacked, stream_fwd, scales, raw, save, P, cs,
                        FineStage{}, cm);
     return scn_launch_status();

@@ -117,6 +117,12 @@ __device__ __forceinline__ void cut8(const float* x, float s, u32x4& h, u32x4& l
     }
 }
 
+// the high plane alone (the one-product arithmetic: no residual is formed)
+__device__ __forceinline__ void cut8_high(const float* x, float s, u32x4& h) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) h[c] = pack_f16_scaled(x[2 * c], x[2 * c + 1], s);
+}
+
 // ---- weight stream ------------------------------------------------------------------------------------------------
 struct Stream {
     global_bytes g;        // the chunk to fetch next (two ahead of the one in use)
@@ -197,58 +203,86 @@ __device__ __forceinline__ void ring_prime(Wave& w) {
 //           (WhA XhA)(WhB XhB)(WhA XlA)(WhB XlB)(WlA XhA)(WlB XhB), slab A into acc[0], slab B into acc[1] (the caller
 //           adds the two: consecutive MFMAs never target the same accumulator)
 // `fill(I<j>)` is issued in front of MFMA j; slots 0 .. 3 also fetch the NEXT unit's fragments.
-template <int U, bool PAIR, bool FIRST, class Fill>
+// PRODUCTS == 1 (forward-only, opt-in: mlp_fwd_h3_kernel.h): the same stream, the same six slots, but only the two
+// (Wh Xh) MFMAs -- in slots 0 and 3, so that the two accumulators alternate at even distance through the stream -- and
+// fragment 3 of the next unit, low in both formats, is not read into the ring.
+template <int U, bool PAIR, bool FIRST, int PRODUCTS = 3, class Fill>
 __device__ __forceinline__ void unit(Wave& w, u32x4 xhA, u32x4 xlA, u32x4 xhB, u32x4 xlB, f32x16 (&acc)[2], Fill&& fill) {
+    static_assert(PRODUCTS == 3 || PRODUCTS == 1, "three fp16 products per product, or the high one alone");
     constexpr int PH = U & 7, RP = U & 1;
     static_for<6>([&](auto j_tag) {
         constexpr int j = decltype(j_tag)::value;
-        // (the stream first: its barrier drains the LDS queue -- `s_waitcnt lgkmcnt(0)` -- so it sits in front of the
-        //  reads this slot issues, not behind them)
-        stream_slot<PH * 6 + j>(w.ws, w.lds, w.tid16);
-        fill(j_tag);
-        if constexpr (j < 4) {
-            // (the next unit may sit in the next chunk: its buffer is complete behind this chunk's barrier at slot 30.
-            //  At j = 5 of unit 7 stream_slot has already switched buffers, hence the reads stay in slots 0 .. 3.)
-            constexpr int NPH = (PH + 1) & 7;
-            const unsigned buf = PH == 7 ? w.ws.next() : w.ws.cur;
-            w.ring[RP ^ 1][j] = *reinterpret_cast<const s16x8*>(w.lds + buf + (NPH * 4 + j) * 1024 + w.lane16);
-        }
-        sched_fence();
-        constexpr int x = j & 1;
-        constexpr int fr = PAIR ? (j < 4 ? (j & 1) : 2 + (j & 1)) : (j < 4 ? 2 * (j & 1) : 1 + 2 * (j & 1));
-        const u32x4 b = PAIR ? ((j == 2 || j == 3) ? xlA : xhA)
-                             : ((j == 2 || j == 3) ? (x ? xlB : xlA) : (x ? xhB : xhA));
-        if constexpr (FIRST && j < 2) {
-            const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            acc[x] = mfma_32x32x16_f16(w.ring[RP][fr], as_frag(b), zero);
+        if constexpr (PRODUCTS == 1) {
+            stream_slot<PH * 6 + j>(w.ws, w.lds, w.tid16);
+            fill(j_tag);
+            if constexpr (j < 3) {
+                // (the NEXT unit's high fragments are 0, 1 if it is a PAIR unit and 0, 2 if not, which this unit does not
+                //  know: fragment 3 is low in both formats and is the one left in LDS)
+                constexpr int NPH = (PH + 1) & 7;
+                const unsigned buf = PH == 7 ? w.ws.next() : w.ws.cur;
+                w.ring[RP ^ 1][j] = *reinterpret_cast<const s16x8*>(w.lds + buf + (NPH * 4 + j) * 1024 + w.lane16);
+            }
+            sched_fence();
+            if constexpr (j == 0 || j == 3) {
+                constexpr int x = j == 3, fr = PAIR ? x : 2 * x;
+                const u32x4 b = (!PAIR && x) ? xhB : xhA;
+                if constexpr (FIRST) {
+                    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                    acc[x] = mfma_32x32x16_f16(w.ring[RP][fr], as_frag(b), zero);
+                } else {
+                    acc[x] = mfma_32x32x16_f16(w.ring[RP][fr], as_frag(b), acc[x]);
+                }
+            }
+            sched_fence();
         } else {
-            acc[x] = mfma_32x32x16_f16(w.ring[RP][fr], as_frag(b), acc[x]);
+            // (the stream first: its barrier drains the LDS queue -- `s_waitcnt lgkmcnt(0)` -- so it sits in front of the
+            //  reads this slot issues, not behind them)
+            stream_slot<PH * 6 + j>(w.ws, w.lds, w.tid16);
+            fill(j_tag);
+            if constexpr (j < 4) {
+                // (the next unit may sit in the next chunk: its buffer is complete behind this chunk's barrier at slot 30.
+                //  At j = 5 of unit 7 stream_slot has already switched buffers, hence the reads stay in slots 0 .. 3.)
+                constexpr int NPH = (PH + 1) & 7;
+                const unsigned buf = PH == 7 ? w.ws.next() : w.ws.cur;
+                w.ring[RP ^ 1][j] = *reinterpret_cast<const s16x8*>(w.lds + buf + (NPH * 4 + j) * 1024 + w.lane16);
+            }
+            sched_fence();
+            constexpr int x = j & 1;
+            constexpr int fr = PAIR ? (j < 4 ? (j & 1) : 2 + (j & 1)) : (j < 4 ? 2 * (j & 1) : 1 + 2 * (j & 1));
+            const u32x4 b = PAIR ? ((j == 2 || j == 3) ? xlA : xhA)
+                                 : ((j == 2 || j == 3) ? (x ? xlB : xlA) : (x ? xhB : xhA));
+            if constexpr (FIRST && j < 2) {
+                const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                acc[x] = mfma_32x32x16_f16(w.ring[RP][fr], as_frag(b), zero);
+            } else {
+                acc[x] = mfma_32x32x16_f16(w.ring[RP][fr], as_frag(b), acc[x]);
+            }
+            sched_fence();
         }
-        sched_fence();
     });
 }
 
 // All K slabs of one output-tile pair: NK units starting at stream unit U0.  operand(I<s>, &xh, &xl) names the
 // planes of K slab s; fill(I<sigma>) is the filler of slot sigma = 6 s + j.
-template <int U0, int NK, class Operand, class Fill>
+template <int U0, int NK, int PRODUCTS = 3, class Operand, class Fill>
 __device__ __forceinline__ void tile_pair(Wave& w, f32x16 (&acc)[2], Operand&& operand, Fill&& fill) {
     static_for<NK>([&](auto s_tag) {
         constexpr int s = decltype(s_tag)::value;
         u32x4 xh, xl;
         operand(s_tag, xh, xl);
-        unit<U0 + s, true, s == 0>(w, xh, xl, xh, xl, acc, [&](auto j_tag) { fill(I<6 * s + decltype(j_tag)::value>{}); });
+        unit<U0 + s, true, s == 0, PRODUCTS>(w, xh, xl, xh, xl, acc, [&](auto j_tag) { fill(I<6 * s + decltype(j_tag)::value>{}); });
     });
 }
 
 // All K slabs (2 NU of them) of a single output tile; the result is acc[0] + acc[1].
-template <int U0, int NU, class Operand, class Fill>
+template <int U0, int NU, int PRODUCTS = 3, class Operand, class Fill>
 __device__ __forceinline__ void tile_single(Wave& w, f32x16 (&acc)[2], Operand&& operand, Fill&& fill) {
     static_for<NU>([&](auto u_tag) {
         constexpr int u = decltype(u_tag)::value;
         u32x4 xhA, xlA, xhB, xlB;
         operand(I<2 * u>{}, xhA, xlA);
         operand(I<2 * u + 1>{}, xhB, xlB);
-        unit<U0 + u, false, u == 0>(w, xhA, xlA, xhB, xlB, acc, [&](auto j_tag) { fill(I<6 * u + decltype(j_tag)::value>{}); });
+        unit<U0 + u, false, u == 0, PRODUCTS>(w, xhA, xlA, xhB, xlB, acc, [&](auto j_tag) { fill(I<6 * u + decltype(j_tag)::value>{}); });
     });
 }
 

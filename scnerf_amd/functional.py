@@ -88,7 +88,9 @@ class RenderRaysFunction(torch.autograd.Function):
         mx_c = ops.ChunkMaxima(n * sc, dev) if (train and resident) else None
         # (the resident kernels' scale guard, ops.resident_guard: None while it is off)
         # (one record buffer per call, every pass of both stages, forward and data gradients)
-        guards = ops.guard_records(dev, [("coarse", n * sc)] + ([("fine", n * (sc + sf))] if sf > 0 else [])) \
+        # (forward-only with ops.inference_arithmetic("fast"): the packs say so, and such passes take no record)
+        fast = resident and pl_c.fast
+        guards = ops.guard_records(dev, [("coarse", n * sc)] + ([("fine", n * (sc + sf))] if sf > 0 else []), fast=fast) \
             if (resident and n > 0) else {}
         gd_c = guards.get("coarse")
         if sc == ops.COARSE_STAGE_SAMPLES and n > 0:
@@ -130,8 +132,8 @@ class RenderRaysFunction(torch.autograd.Function):
             wf_f, pl_f = ops.inference_packs(fine_net, flat_f)
         mx_f = ops.ChunkMaxima(n * tot, dev) if (train and resident) else None
         gd_f = guards.get("fine")
-        # (with the guard on, the three launches: the same numbers as the fused stage)
-        if ops.fused_fine_stage() and gd_f is None and resident and sc == ops.COARSE_STAGE_SAMPLES and sf in ops.FINE_STAGE_IMPORTANCE and n > 0:
+        # (with the guard on, and on the one-product arithmetic, the three launches: the same numbers as the fused stage)
+        if ops.fused_fine_stage() and gd_f is None and not fast and resident and sc == ops.COARSE_STAGE_SAMPLES and sf in ops.FINE_STAGE_IMPORTANCE and n > 0:
             # the whole fine stage -- inverse-cdf sampler, merge, network, compositing -- as one launch (opt-in: measured
             # slower than the three launches below, ops.fused_fine_stage)
             z_f, pts_f, z_s, z_std, _, _, raw_f, rgb_f, disp_f, acc_f, depth_f, _ = ops.fine_stage_fwd(

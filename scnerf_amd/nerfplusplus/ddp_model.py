@@ -77,7 +77,7 @@ class _NerfNetFunction(torch.autograd.Function):
         resident = train and isinstance(pl_f, ops.ResidentWeights)
         mx_f = ops.ChunkMaxima(n * sf, dev) if resident else None        # (for the fp16 weight-gradient GEMMs)
         mx_b = ops.ChunkMaxima(n * sb, dev) if resident else None
-        guards = ops.guard_records(dev, [("nerfpp_fg", n * sf), ("nerfpp_bg", n * sb)]) \
+        guards = ops.guard_records(dev, [("nerfpp_fg", n * sf), ("nerfpp_bg", n * sb)], fast=getattr(pl_f, "fast", False)) \
             if (isinstance(pl_f, ops.ResidentWeights) and n > 0) else {}
         raw_f = ops.mlp_fwd(fg_pts, views, sf, wf_f, save_f, pd=3, planes=pl_f, maxima=mx_f, guard=guards.get("nerfpp_fg"))
         raw_b = ops.mlp_fwd(bg_pts, views, sb, wf_b, save_b, pd=4, planes=pl_b, maxima=mx_b, guard=guards.get("nerfpp_bg"))

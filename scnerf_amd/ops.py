@@ -284,6 +284,27 @@ def mlp_arithmetic(mode: Optional[str] = None) -> str:
     return _MLP_ARITHMETIC[0]
 
 
+INFERENCE_ARITHMETICS = ("same", "fast")
+_INFERENCE_ARITHMETIC = [os.environ.get("SCNERF_INFER_ARITHMETIC", "same")]
+if _INFERENCE_ARITHMETIC[0] not in INFERENCE_ARITHMETICS:
+    raise ValueError("SCNERF_INFER_ARITHMETIC must be one of %s, not %r" % ("|".join(INFERENCE_ARITHMETICS), _INFERENCE_ARITHMETIC[0]))
+
+
+def inference_arithmetic(mode: Optional[str] = None) -> str:
+    """How FORWARD-ONLY network passes run (render_path, render_path_sharded, NeRF++'s render_single_image, a network query
+    under torch.no_grad()): "same" (the default) -- as every other pass, ops.mlp_arithmetic; "fast" -- where that is
+    "resident", on ONE fp16 product per product instead of three (csrc/mlp_fwd_h3_kernel.h, PRODUCTS == 1): operands
+    rounded to fp16 after their power-of-two scale, fp32 accumulation, a third of the matrix instructions, outputs within
+    fp16 rounding of the default's instead of fp32 rounding.  A call that tracks gradients runs exactly as without the
+    switch, and so does every call under mlp_arithmetic("fp32").  "fast" passes take no scale-guard record.
+    Without an argument: the mode in force.  Environment preset: SCNERF_INFER_ARITHMETIC."""
+    if mode is not None:
+        if mode not in INFERENCE_ARITHMETICS:
+            raise ValueError("inference_arithmetic is one of " + ", ".join(INFERENCE_ARITHMETICS))
+        _INFERENCE_ARITHMETIC[0] = mode
+    return _INFERENCE_ARITHMETIC[0]
+
+
 RESIDENT_GUARDS = ("off", "fallback", "report", "strict")
 # Off by default: on the headline step the fallback mode costs 1.4 - 1.5 % (medians of alternating runs in both orders,
 # profiles/r07_resident_guard.txt) -- over the half per cent a default may cost.
@@ -359,12 +380,19 @@ class GuardRecord:
             lo, hi, int((self.flags != 0).sum()), m["blocks"]))
 
 
-def guard_records(device, passes) -> dict:
+def guard_records(device, passes, fast: bool = False) -> dict:
     """Records for the network passes of one call in the guard mode in force, carved from ONE zero-filled buffer:
-    passes = [(name, P), ...] -> {name: forward record, name + "_bwd": data-gradient record} ({} when "off").  The
+    passes = [(name, P), ...] -> {name: forward record, name + "_bwd": data-gradient record} ({} when "off", and for a
+    call whose passes run on the one-product arithmetic -- `fast`, ResidentWeights.fast: the guard does not apply to
+    them, and what earlier launches of these passes left no longer shows in resident_margins()).  The
     data-gradient record shares its pass's block flags: a block the forward ran again in fp32 runs again in the data
     gradients too.  resident_margins() reads the latest launched record of every pass."""
     mode = _RESIDENT_GUARD[0]
+    if fast:
+        for name, _ in passes:
+            _GUARD_LAST.pop(name, None)
+            _GUARD_LAST.pop(name + "_bwd", None)
+        return {}
     if mode == "off":
         return {}
     rep = GUARD_REPORT_FLOATS if mode in ("report", "strict") else 0
@@ -437,11 +465,14 @@ def inference_packs(net, flat_params: Tensor, pd: int = 3, remap=None):
     once per weight version (weight_pack_cache)."""
     def build():
         PACK_CACHE_STATS["packs"] += 1
-        return (pack_weights(flat_params, "fwd", pd=pd, remap=remap), pack_for_arithmetic(flat_params, False, pd, remap=remap))
+        planes = pack_for_arithmetic(flat_params, False, pd, remap=remap)
+        if isinstance(planes, ResidentWeights):
+            planes.fast = _INFERENCE_ARITHMETIC[0] == "fast"
+        return (pack_weights(flat_params, "fwd", pd=pd, remap=remap), planes)
     if not _PACK_CACHE[0]:
         return build()
-    key = (flat_params.data_ptr(), flat_params._version, tuple(p._version for p in net.parameters()), _MLP_ARITHMETIC[0], pd,
-           torch.cuda.current_stream(flat_params.device).cuda_stream if flat_params.is_cuda else 0)
+    key = (flat_params.data_ptr(), flat_params._version, tuple(p._version for p in net.parameters()), _MLP_ARITHMETIC[0],
+           _INFERENCE_ARITHMETIC[0], pd, torch.cuda.current_stream(flat_params.device).cuda_stream if flat_params.is_cuda else 0)
     hit = getattr(net, "_infer_packs", None)
     if hit is not None and hit[0] == key:
         PACK_CACHE_STATS["hits"] += 1
@@ -457,10 +488,13 @@ _canon_cache = {}
 class ResidentWeights:
     """What the resident arithmetic reads besides the packed fp32 tables: the two fp16 fragment streams and the
     scale table (pack_resident)."""
-    __slots__ = ("fwd", "bwd", "scales", "pd")
+    __slots__ = ("fwd", "bwd", "scales", "pd", "fast")
 
     def __init__(self, fwd, bwd, scales, pd):
         self.fwd, self.bwd, self.scales, self.pd = fwd, bwd, scales, pd
+        # forward-only launches with these weights run on one fp16 product per product (inference_arithmetic "fast").
+        # Set by inference_packs alone -- the packs of a forward-only call -- so no training pass ever sees it.
+        self.fast = False
 
 
 class ChunkMaxima:
@@ -584,6 +618,14 @@ def mlp_fwd_resident(pts: Tensor, viewdirs: Tensor, samples_per_ray: int, wpacke
         if save.numel() < lay.save_floats(P):
             raise ValueError("activation workspace too small")
     raw = torch.empty((P, 4), dtype=torch.float32, device=pts.device)
+    if rw.fast:
+        if save is not None or guard is not None:
+            raise ValueError("the one-product arithmetic is forward-only and takes no guard record")
+        with PROFILE.region("mlp_fwd_h3_kernel%s/P=%d/infer fast" % ("" if pd == 3 else "/pd4", P), 2 * _MAC_PER_SAMPLE[pd] * P):
+            st = _capi.load().scnerf_mlp_fwd_h3_fast(pd, _p(pts), vptr, vstride, int(samples_per_ray), _p(wpacked), _p(rw.fwd),
+                                                     _p(rw.scales), _p(raw), P, None, 0, 0, _stream())
+        _capi.check(st, "scnerf_mlp_fwd_h3_fast")
+        return raw
     with PROFILE.region("mlp_fwd_h3_kernel%s/P=%d/%s" % ("" if pd == 3 else "/pd4", P, "train" if save is not None else "infer"),
                         2 * _MAC_PER_SAMPLE[pd] * P):
         mx = maxima if save is not None else None
@@ -635,6 +677,16 @@ def coarse_stage_fwd(rays: Tensor, t_vals: Tensor, t_rand: Optional[Tensor], lin
     if isinstance(planes, ResidentWeights):
         if planes.pd != 3:
             raise ValueError("the coarse stage samples 3-D points")
+        if planes.fast:
+            if save is not None or guard is not None:
+                raise ValueError("the one-product arithmetic is forward-only and takes no guard record")
+            with PROFILE.region("mlp_fwd_h3_kernel<coarse stage>/P=%d/infer fast" % P, 2 * _MAC_PER_SAMPLE[3] * P):
+                st = _capi.load().scnerf_coarse_stage_fwd_h3_fast(
+                    _p(rays), rays.shape[1], _p(t_vals), _p(t_rand), int(bool(lindisp)), _p(wpacked), _p(planes.fwd),
+                    _p(planes.scales), _p(noise), int(bool(white_bkgd)), _p(z), _p(pts), _p(raw), _p(rgb), _p(disp), _p(acc),
+                    _p(depth), _p(w), n, s, None, 0, 0, _stream())
+            _capi.check(st, "scnerf_coarse_stage_fwd_h3_fast")
+            return z, pts, raw, rgb, disp, acc, w, depth
         with PROFILE.region("mlp_fwd_h3_kernel<coarse stage>/P=%d/%s" % (P, "train" if save is not None else "infer"),
                             2 * _MAC_PER_SAMPLE[3] * P):
             args = (_p(rays), rays.shape[1], _p(t_vals), _p(t_rand), int(bool(lindisp)), _p(wpacked), _p(planes.fwd),
@@ -693,6 +745,8 @@ def fine_stage_fwd(rays: Tensor, z_c: Tensor, w_c: Tensor, u: Tensor, wpacked: T
             _f(t_, name)
     if not isinstance(planes, ResidentWeights) or planes.pd != 3:
         raise TypeError("the fused fine stage runs on the resident arithmetic (3-D points)")
+    if planes.fast:
+        raise ValueError("the fused fine stage has no one-product instantiation: fine_sample, mlp_fwd, composite_fwd")
     n, sc = z_c.shape
     sf = u.shape[-1]
     if sc != COARSE_STAGE_SAMPLES or sf not in FINE_STAGE_IMPORTANCE or rays.shape[1] < 11:

@@ -11,11 +11,22 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def run(images=6, chunk=32768, height=378, width=504):
+def run(images=6, chunk=32768, height=378, width=504, arithmetic=None):
+    """arithmetic: ops.inference_arithmetic for the run ("same" | "fast"); None: the mode in force"""
     import types
     a = types.SimpleNamespace(images=images, chunk=chunk, height=height, width=width)
-    from scnerf_amd import create_nerf as cn, render as R, run_nerf_helpers as h, synthetic as synth
+    from scnerf_amd import create_nerf as cn, ops, render as R, run_nerf_helpers as h, synthetic as synth
     H, W = a.height, a.width
+    saved = ops.inference_arithmetic()
+    if arithmetic is not None:
+        ops.inference_arithmetic(arithmetic)
+    try:
+        return _run(a, H, W, cn, ops, R, h, synth)
+    finally:
+        ops.inference_arithmetic(saved)
+
+
+def _run(a, H, W, cn, ops, R, h, synth):
 
     def net(seed):
         m = h.NeRF(D=8, W=256, input_ch=63, input_ch_views=27, output_ch=5, skips=[4], use_viewdirs=True)
@@ -38,6 +49,7 @@ def run(images=6, chunk=32768, height=378, width=504):
     return {"metric": "rays/sec (64+128 samples/ray) full-image inference", "value": rays / dt,
             "unit": "rays/s", "images": a.images, "image": [H, W], "chunk": a.chunk,
             "s_per_image": dt / a.images, "tflops_algorithmic": flop / dt / 1e12,
+            "inference_arithmetic": ops.inference_arithmetic(),
             "includes": "ray generation, NDC, render, D2H copy into numpy"}
 
 
@@ -47,8 +59,10 @@ def main():
     ap.add_argument("--chunk", type=int, default=32768)
     ap.add_argument("--height", type=int, default=378)
     ap.add_argument("--width", type=int, default=504)
+    ap.add_argument("--arithmetic", choices=("same", "fast"), default=None,
+                    help="ops.inference_arithmetic for the run (default: the mode in force, SCNERF_INFER_ARITHMETIC)")
     a = ap.parse_args()
-    print(json.dumps(run(a.images, a.chunk, a.height, a.width)))
+    print(json.dumps(run(a.images, a.chunk, a.height, a.width, a.arithmetic)))
 
 
 if __name__ == "__main__":

@@ -14,10 +14,12 @@ KEEP = ("mlp_fwd_kernel", "mlp_bwd_kernel", "mlp_fwd_h3_kernel", "mlp_bwd_h3_ker
         "wgrad_tiles_kernel", "wgrad_reduce_multi_kernel", "wgrad_kernel", "vecmat_kernel", "elementwise_kernel")
 
 # bench.py's region names of the kernels whose HBM traffic goes into profiles/pmc_traffic_r<NN>.json (P = 786432)
-REGIONS = {"mlp_fwd_h3_kernel<3, true, 0>": "mlp_fwd_h3_kernel/P=786432/train",
-           "mlp_fwd_h3_kernel<3, false, 0>": "mlp_fwd_h3_kernel/P=786432/infer",
-           "mlp_fwd_h3_kernel<3, true, 2>": "mlp_fwd_h3_kernel<fine stage>/P=786432/train",
-           "mlp_fwd_h3_kernel<3, false, 2>": "mlp_fwd_h3_kernel<fine stage>/P=786432/infer",
+# (the forward kernel's last template argument: fp16 products per product -- 3, or 1 for ops.inference_arithmetic("fast"))
+REGIONS = {"mlp_fwd_h3_kernel<3, true, 0, 3>": "mlp_fwd_h3_kernel/P=786432/train",
+           "mlp_fwd_h3_kernel<3, false, 0, 3>": "mlp_fwd_h3_kernel/P=786432/infer",
+           "mlp_fwd_h3_kernel<3, false, 0, 1>": "mlp_fwd_h3_kernel/P=786432/infer fast",
+           "mlp_fwd_h3_kernel<3, true, 2, 3>": "mlp_fwd_h3_kernel<fine stage>/P=786432/train",
+           "mlp_fwd_h3_kernel<3, false, 2, 3>": "mlp_fwd_h3_kernel<fine stage>/P=786432/infer",
            "mlp_bwd_h3_kernel<3>": "mlp_bwd_h3_kernel/P=786432",
            "wgrad256_half_kernel<0>": "wgrad256_kernel<8 GEMMs, half>/P=786432"}
 
