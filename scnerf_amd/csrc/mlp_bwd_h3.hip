@@ -13,11 +13,11 @@
 #include "mlp_bwd_h3_api.h"
 #include "scnerf_hip.h"
 
-extern "C" int scnerf_mlp_bwd_h3_guarded(int pt_dims, const float* d_raw, const float* pts, const float* viewdirs,
-                                         int vd_stride, int samples_per_ray, const float* wpacked_bwd, const short* stream_bwd,
-                                         const float* scales, const float* save, float* grads, float* d_pts, float* d_views,
-                                         long long n_samples, float* chunk_amax, int n_chunks, long long chunk_samples,
-                                         int* guard_flags, int* guard_any, float* guard_report, void* stream) {
+extern "C" int scnerf_mlp_bwd_h3_lean(int pt_dims, const float* d_raw, const float* pts, const float* viewdirs,
+                                      int vd_stride, int samples_per_ray, const float* wpacked_bwd, const short* stream_bwd,
+                                      const float* scales, const float* save, float* grads, float* d_pts, float* d_views,
+                                      long long n_samples, float* chunk_amax, int n_chunks, long long chunk_samples,
+                                      int* guard_flags, int* guard_any, float* guard_report, int lean, void* stream) {
     SCN_RETURN_IF(!d_raw || !pts || !viewdirs || !wpacked_bwd || !stream_bwd || !scales || !save || !grads, SCN_EINVAL);
     SCN_RETURN_IF(!d_pts != !d_views, SCN_EINVAL);             // both NULL: no input gradient
     SCN_RETURN_IF(samples_per_ray < 1 || vd_stride < 3 || n_samples < 0 || (pt_dims != 3 && pt_dims != 4), SCN_EINVAL);
@@ -26,9 +26,19 @@ extern "C" int scnerf_mlp_bwd_h3_guarded(int pt_dims, const float* d_raw, const 
     SCN_RETURN_IF(!guard_flags != !guard_any || (guard_report && !guard_flags), SCN_EINVAL);
     if (n_samples == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    const scn::h3b::ChunkMaxima cm{chunk_amax, n_chunks, (long)chunk_samples, {guard_flags, guard_any, guard_report}};
+    const scn::h3b::ChunkMaxima cm{chunk_amax, n_chunks, lean != 0, (long)chunk_samples, {guard_flags, guard_any, guard_report}};
     return pt_dims == 3 ? scn::h3b::bwd_h3_pd3(d_raw, pts, viewdirs, vd_stride, samples_per_ray, wpacked_bwd, stream_bwd, scales, save, grads, d_pts, d_views, n_samples, cm, st)
                         : scn::h3b::bwd_h3_pd4(d_raw, pts, viewdirs, vd_stride, samples_per_ray, wpacked_bwd, stream_bwd, scales, save, grads, d_pts, d_views, n_samples, cm, st);
+}
+
+extern "C" int scnerf_mlp_bwd_h3_guarded(int pt_dims, const float* d_raw, const float* pts, const float* viewdirs,
+                                         int vd_stride, int samples_per_ray, const float* wpacked_bwd, const short* stream_bwd,
+                                         const float* scales, const float* save, float* grads, float* d_pts, float* d_views,
+                                         long long n_samples, float* chunk_amax, int n_chunks, long long chunk_samples,
+                                         int* guard_flags, int* guard_any, float* guard_report, void* stream) {
+    return scnerf_mlp_bwd_h3_lean(pt_dims, d_raw, pts, viewdirs, vd_stride, samples_per_ray, wpacked_bwd, stream_bwd, scales, save,
+                                  grads, d_pts, d_views, n_samples, chunk_amax, n_chunks, chunk_samples, guard_flags, guard_any,
+                                  guard_report, 0, stream);
 }
 
 extern "C" int scnerf_mlp_bwd_h3(int pt_dims, const float* d_raw, const float* pts, const float* viewdirs, int vd_stride,

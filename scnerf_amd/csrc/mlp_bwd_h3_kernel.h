@@ -58,11 +58,14 @@ struct Rank1 {
     f32x4 wqs[2];              // read from LDS one piece ahead (piece parity), as mlp_fwd_h3.hip's bias
 };
 struct NoGate {};
+struct NoWindow {};
+struct Window { unsigned window; };     // the d feature section's store window (mlp_h3.h store_written_through_window)
 struct Gate { u32x4 gate; };   // ReLU bits of the layer below: element 16 t + r <-> word t >> 1, bit 31 - (16 (t & 1) + r)
 
 // KIND 0: ReLU gate;  1: gate + the density head's rank-1 term (feature_linear^T);  2: linear (d feature)
 template <int KIND>
-struct BwdEpi : std::conditional_t<KIND == 1, Rank1, NoRank1>, std::conditional_t<KIND != 2, Gate, NoGate> {
+struct BwdEpi : std::conditional_t<KIND == 1, Rank1, NoRank1>, std::conditional_t<KIND != 2, Gate, NoGate>,
+                std::conditional_t<KIND == 2, Window, NoWindow> {
     float os, s_next, am;
     global_bytes_rw save;      // this wave tile's block of the gradient section the result goes to
     unsigned lane16;
@@ -108,8 +111,12 @@ struct BwdEpi : std::conditional_t<KIND == 1, Rank1, NoRank1>, std::conditional_
             oh[sl][c0 + 1] = hp;
             ol[sl][c0 + 1] = pack_f16(residual_f16<0>(v[2], s_next, hp), residual_f16<1>(v[3], s_next, hp));
         } else if constexpr (SUB == 10) {
-            if constexpr (!lab::kNoStore)
+            if constexpr (lab::kNoStore) {
+            } else if constexpr (KIND == 2) {       // (the lean workspace shuts the window: nothing is written)
+                store_written_through_window(uniform_global_rw(save + (4 * T + q) * 1024), pinned_here(lane16), f32x4{v[0], v[1], v[2], v[3]}, this->window);
+            } else {
                 store_written_through_at(uniform_global_rw(save + (4 * T + q) * 1024), pinned_here(lane16), f32x4{v[0], v[1], v[2], v[3]});
+            }
         }
     }
 };
@@ -251,6 +258,7 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_bwd_h3_kernel(
     epif.am = 0.f;
     epif.save = section(kGradDfeat, 256);
     epif.lane16 = w.lane16;
+    epif.window = cm.lean ? kStoreWindowShut : kStoreWindowOpen;
     tile_pair<6, 8>(w, acc[0], hv_operand, NoFill{});
     tile_pair<14, 8>(w, acc[1], hv_operand, [&](auto sg) { epi_slot<LinEpi, 0, decltype(sg)::value, 6>(epif, acc[0], bh[0], bl[0]); });
     tile_pair<22, 8>(w, acc[0], hv_operand, [&](auto sg) { epi_slot<LinEpi, 1, decltype(sg)::value, 6>(epif, acc[1], bh[0], bl[0]); });

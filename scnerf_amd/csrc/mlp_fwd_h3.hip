@@ -155,11 +155,11 @@ extern "C" int scnerf_h3_pack(const float* flat_params, const int* jobs, const i
     return scn_launch_status();
 }
 
-extern "C" int scnerf_mlp_fwd_h3_guarded(int pt_dims, const float* pts, const float* viewdirs, int vd_stride,
-                                         int samples_per_ray, const float* wpacked, const short* stream_fwd,
-                                         const float* scales, float* raw, float* save, long long n_samples, float* chunk_amax,
-                                         int n_chunks, long long chunk_samples, int* guard_flags, int* guard_any,
-                                         float* guard_report, void* stream) {
+extern "C" int scnerf_mlp_fwd_h3_lean(int pt_dims, const float* pts, const float* viewdirs, int vd_stride,
+                                      int samples_per_ray, const float* wpacked, const short* stream_fwd,
+                                      const float* scales, float* raw, float* save, long long n_samples, float* chunk_amax,
+                                      int n_chunks, long long chunk_samples, int* guard_flags, int* guard_any,
+                                      float* guard_report, int lean, void* stream) {
     SCN_RETURN_IF(!pts || !viewdirs || !wpacked || !stream_fwd || !scales || !raw, SCN_EINVAL);
     SCN_RETURN_IF(samples_per_ray < 1 || vd_stride < 3 || n_samples < 0 || (pt_dims != 3 && pt_dims != 4), SCN_EINVAL);
     SCN_RETURN_IF(n_samples >= (1LL << 31), SCN_ENOSUP);       // (the kernels index samples with 31 bits)
@@ -167,9 +167,18 @@ extern "C" int scnerf_mlp_fwd_h3_guarded(int pt_dims, const float* pts, const fl
     SCN_RETURN_IF(!guard_flags != !guard_any || (guard_report && !guard_flags), SCN_EINVAL);
     if (n_samples == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    const scn::h3f::ChunkMaxima cm{chunk_amax, n_chunks, (long)chunk_samples, {guard_flags, guard_any, guard_report}};
+    const scn::h3f::ChunkMaxima cm{chunk_amax, n_chunks, lean != 0, (long)chunk_samples, {guard_flags, guard_any, guard_report}};
     return pt_dims == 3 ? scn::h3f::fwd_h3_pd3(pts, viewdirs, vd_stride, samples_per_ray, wpacked, stream_fwd, scales, raw, save, n_samples, cm, st)
                         : scn::h3f::fwd_h3_pd4(pts, viewdirs, vd_stride, samples_per_ray, wpacked, stream_fwd, scales, raw, save, n_samples, cm, st);
+}
+
+extern "C" int scnerf_mlp_fwd_h3_guarded(int pt_dims, const float* pts, const float* viewdirs, int vd_stride,
+                                         int samples_per_ray, const float* wpacked, const short* stream_fwd,
+                                         const float* scales, float* raw, float* save, long long n_samples, float* chunk_amax,
+                                         int n_chunks, long long chunk_samples, int* guard_flags, int* guard_any,
+                                         float* guard_report, void* stream) {
+    return scnerf_mlp_fwd_h3_lean(pt_dims, pts, viewdirs, vd_stride, samples_per_ray, wpacked, stream_fwd, scales, raw, save,
+                                  n_samples, chunk_amax, n_chunks, chunk_samples, guard_flags, guard_any, guard_report, 0, stream);
 }
 
 extern "C" int scnerf_mlp_fwd_h3(int pt_dims, const float* pts, const float* viewdirs, int vd_stride, int samples_per_ray,
@@ -179,13 +188,13 @@ extern "C" int scnerf_mlp_fwd_h3(int pt_dims, const float* pts, const float* vie
                                      n_samples, chunk_amax, n_chunks, chunk_samples, nullptr, nullptr, nullptr, stream);
 }
 
-extern "C" int scnerf_coarse_stage_fwd_h3_guarded(const float* rays, int ray_stride, const float* t_vals, const float* t_rand,
-                                                  int lindisp, const float* wpacked, const short* stream_fwd,
-                                                  const float* scales, float* save, const float* noise, int white_bkgd, float* z,
-                                                  float* pts, float* raw, float* rgb_map, float* disp_map, float* acc_map,
-                                                  float* depth_map, float* weights, int n_rays, int n_samples,
-                                                  float* chunk_amax, int n_chunks, long long chunk_samples, int* guard_flags,
-                                                  int* guard_any, float* guard_report, void* stream) {
+extern "C" int scnerf_coarse_stage_fwd_h3_lean(const float* rays, int ray_stride, const float* t_vals, const float* t_rand,
+                                               int lindisp, const float* wpacked, const short* stream_fwd,
+                                               const float* scales, float* save, const float* noise, int white_bkgd, float* z,
+                                               float* pts, float* raw, float* rgb_map, float* disp_map, float* acc_map,
+                                               float* depth_map, float* weights, int n_rays, int n_samples,
+                                               float* chunk_amax, int n_chunks, long long chunk_samples, int* guard_flags,
+                                               int* guard_any, float* guard_report, int lean, void* stream) {
     SCN_RETURN_IF(!rays || !t_vals || !wpacked || !stream_fwd || !scales || !z || !pts || !raw || !rgb_map || !disp_map || !acc_map, SCN_EINVAL);
     SCN_RETURN_IF(n_rays < 0 || ray_stride < 11, SCN_EINVAL);
     SCN_RETURN_IF(n_samples != scn::h3f::kCoarseSamples || n_rays >= (1 << 25), SCN_ENOSUP);     // (31-bit sample indices)
@@ -194,8 +203,21 @@ extern "C" int scnerf_coarse_stage_fwd_h3_guarded(const float* rays, int ray_str
     if (n_rays == 0) return 0;
     const scn::h3f::CoarseStage cs{rays, ray_stride, n_rays, t_vals, t_rand, lindisp, z, pts, noise, white_bkgd,
                                    rgb_map, disp_map, acc_map, depth_map, weights};
-    const scn::h3f::ChunkMaxima cm{chunk_amax, n_chunks, (long)chunk_samples, {guard_flags, guard_any, guard_report}};
+    const scn::h3f::ChunkMaxima cm{chunk_amax, n_chunks, lean != 0, (long)chunk_samples, {guard_flags, guard_any, guard_report}};
     return scn::h3f::fwd_h3_coarse(cs, rays, ray_stride, wpacked, stream_fwd, scales, raw, save, cm, (hipStream_t)stream);
+}
+
+extern "C" int scnerf_coarse_stage_fwd_h3_guarded(const float* rays, int ray_stride, const float* t_vals, const float* t_rand,
+                                                  int lindisp, const float* wpacked, const short* stream_fwd,
+                                                  const float* scales, float* save, const float* noise, int white_bkgd, float* z,
+                                                  float* pts, float* raw, float* rgb_map, float* disp_map, float* acc_map,
+                                                  float* depth_map, float* weights, int n_rays, int n_samples,
+                                                  float* chunk_amax, int n_chunks, long long chunk_samples, int* guard_flags,
+                                                  int* guard_any, float* guard_report, void* stream) {
+    return scnerf_coarse_stage_fwd_h3_lean(rays, ray_stride, t_vals, t_rand, lindisp, wpacked, stream_fwd, scales, save, noise,
+                                           white_bkgd, z, pts, raw, rgb_map, disp_map, acc_map, depth_map, weights, n_rays,
+                                           n_samples, chunk_amax, n_chunks, chunk_samples, guard_flags, guard_any, guard_report,
+                                           0, stream);
 }
 
 extern "C" int scnerf_coarse_stage_fwd_h3(const float* rays, int ray_stride, const float* t_vals, const float* t_rand,
@@ -241,14 +263,14 @@ extern "C" int scnerf_coarse_stage_fwd_h3_fast(const float* rays, int ray_stride
     return scn::h3f::fwd_h3_coarse_fast(cs, rays, ray_stride, wpacked, stream_fwd, scales, raw, (hipStream_t)stream);
 }
 
-extern "C" int scnerf_fine_stage_fwd_h3_guarded(const float* rays, int ray_stride, const float* z_c, const float* w_c,
-                                                const float* u, int u_row_stride, const float* wpacked, const short* stream_fwd,
-                                                const float* scales, float* save, const float* noise, int white_bkgd, float* z_f,
-                                                float* pts_f, float* z_samples, float* z_std, long long* inds, float* cdf,
-                                                float* raw, float* rgb_map, float* disp_map, float* acc_map, float* depth_map,
-                                                float* weights, int n_rays, int n_coarse, int n_importance, float* chunk_amax,
-                                                int n_chunks, long long chunk_samples, int* guard_flags, int* guard_any,
-                                                float* guard_report, void* stream) {
+extern "C" int scnerf_fine_stage_fwd_h3_lean(const float* rays, int ray_stride, const float* z_c, const float* w_c,
+                                             const float* u, int u_row_stride, const float* wpacked, const short* stream_fwd,
+                                             const float* scales, float* save, const float* noise, int white_bkgd, float* z_f,
+                                             float* pts_f, float* z_samples, float* z_std, long long* inds, float* cdf,
+                                             float* raw, float* rgb_map, float* disp_map, float* acc_map, float* depth_map,
+                                             float* weights, int n_rays, int n_coarse, int n_importance, float* chunk_amax,
+                                             int n_chunks, long long chunk_samples, int* guard_flags, int* guard_any,
+                                             float* guard_report, int lean, void* stream) {
     SCN_RETURN_IF(!rays || !z_c || !w_c || !u || !wpacked || !stream_fwd || !scales, SCN_EINVAL);
     SCN_RETURN_IF(!z_f || !pts_f || !z_samples || !z_std || !raw || !rgb_map || !disp_map || !acc_map, SCN_EINVAL);
     SCN_RETURN_IF(n_rays < 0 || ray_stride < 11 || (u_row_stride != 0 && u_row_stride != n_importance), SCN_EINVAL);
@@ -263,9 +285,23 @@ extern "C" int scnerf_fine_stage_fwd_h3_guarded(const float* rays, int ray_strid
     const scn::h3f::FineStage fs{rays, ray_stride, n_rays, z_c, w_c, u, u_row_stride, n_importance, z_f, pts_f, z_samples, z_std,
                                  reinterpret_cast<int64_t*>(inds), cdf, noise, white_bkgd, rgb_map, disp_map, acc_map,
                                  depth_map, weights, rays_per_block, tiles};
-    const scn::h3f::ChunkMaxima cm{chunk_amax, n_chunks, (long)chunk_samples, {guard_flags, guard_any, guard_report}};
+    const scn::h3f::ChunkMaxima cm{chunk_amax, n_chunks, lean != 0, (long)chunk_samples, {guard_flags, guard_any, guard_report}};
     return save ? scn::h3f::fwd_h3_fine_train(fs, wpacked, stream_fwd, scales, raw, save, cm, (hipStream_t)stream)
                 : scn::h3f::fwd_h3_fine_infer(fs, wpacked, stream_fwd, scales, raw, cm, (hipStream_t)stream);
+}
+
+extern "C" int scnerf_fine_stage_fwd_h3_guarded(const float* rays, int ray_stride, const float* z_c, const float* w_c,
+                                                const float* u, int u_row_stride, const float* wpacked, const short* stream_fwd,
+                                                const float* scales, float* save, const float* noise, int white_bkgd, float* z_f,
+                                                float* pts_f, float* z_samples, float* z_std, long long* inds, float* cdf,
+                                                float* raw, float* rgb_map, float* disp_map, float* acc_map, float* depth_map,
+                                                float* weights, int n_rays, int n_coarse, int n_importance, float* chunk_amax,
+                                                int n_chunks, long long chunk_samples, int* guard_flags, int* guard_any,
+                                                float* guard_report, void* stream) {
+    return scnerf_fine_stage_fwd_h3_lean(rays, ray_stride, z_c, w_c, u, u_row_stride, wpacked, stream_fwd, scales, save, noise,
+                                         white_bkgd, z_f, pts_f, z_samples, z_std, inds, cdf, raw, rgb_map, disp_map, acc_map,
+                                         depth_map, weights, n_rays, n_coarse, n_importance, chunk_amax, n_chunks, chunk_samples,
+                                         guard_flags, guard_any, guard_report, 0, stream);
 }
 
 extern "C" int scnerf_fine_stage_fwd_h3(const float* rays, int ray_stride, const float* z_c, const float* w_c, const float* u,

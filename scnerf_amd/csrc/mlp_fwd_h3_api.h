@@ -13,7 +13,10 @@ namespace h3f {
 // Where the weight-gradient GEMMs' chunk maxima go (wgrad256_half.h): amax [8][n_chunks], job j = the GEMM whose X
 // operand is the input of trunk layer j + 1 (j = 7: feature_linear); chunk = samples per weight-gradient workgroup.
 // `guard`: the record of the scale guard (resident_guard.h; null pointers: no check).
-struct ChunkMaxima { float* amax; int n_chunks; long chunk; ResidentGuard guard; };
+// `lean` (training): the feature section is not stored -- the lean weight-gradient group (wgrad.hip) derives what was
+// computed from it; everything else the launch leaves is bit-identical.  (In the padding behind n_chunks: the argument
+// block keeps its layout.)
+struct ChunkMaxima { float* amax; int n_chunks; int lean; long chunk; ResidentGuard guard; };
 
 struct CoarseStage {
     const float* rays; int ray_stride; int n_rays;

@@ -69,10 +69,13 @@ struct Density {
 };
 template <bool ON> struct MaskBits { unsigned bits0, bits1, words[4]; };
 template <> struct MaskBits<false> {};
+struct NoWindow {};
+struct Window { unsigned window; };     // the feature section's store window (mlp_h3.h store_written_through_window)
 
 // PRODUCTS == 1: the cut leaves the high plane only (no residual; `ol` is never touched)
 template <bool TRAIN, int KIND, int PRODUCTS = 3>
-struct FwdEpi : std::conditional_t<KIND == 1, Density, NoDensity>, MaskBits<TRAIN && KIND != 2> {
+struct FwdEpi : std::conditional_t<KIND == 1, Density, NoDensity>, MaskBits<TRAIN && KIND != 2>,
+                std::conditional_t<TRAIN && KIND == 2, Window, NoWindow> {
     float os, s_next, am;
     const float* bias;         // LDS lane-vector table of the layer, + 4 h
     global_bytes_rw save;      // this wave tile's block of the layer's section (TRAIN)
@@ -125,7 +128,10 @@ struct FwdEpi : std::conditional_t<KIND == 1, Density, NoDensity>, MaskBits<TRAI
             if constexpr (TRAIN && !lab::kNoStore) {
                 // (wave-uniform base + the lane's 32-bit offset: as 64-bit per-lane pointers the eight piece bases of a
                 //  layer are hoisted into sixteen long-lived registers)
-                store_written_through_at(uniform_global_rw(save + (4 * T + q) * 1024), pinned_here(lane16), f32x4{v[0], v[1], v[2], v[3]});
+                if constexpr (KIND == 2)      // (the lean workspace shuts the window: nothing is written)
+                    store_written_through_window(uniform_global_rw(save + (4 * T + q) * 1024), pinned_here(lane16), f32x4{v[0], v[1], v[2], v[3]}, this->window);
+                else
+                    store_written_through_at(uniform_global_rw(save + (4 * T + q) * 1024), pinned_here(lane16), f32x4{v[0], v[1], v[2], v[3]});
             }
         } else {
             if constexpr (KIND == 1) {
@@ -464,6 +470,12 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_fwd_h3_kernel(
     epif.bias = tab_h + kTabFeat;
     epif.save = TRAIN ? section(kSaveFeat, 256) : nullptr;
     epif.lane16 = w.lane16;
+    if constexpr (TRAIN) {
+        // (read from the argument block here, as the guard's record: held from the kernel's start it is one more scalar
+        //  register across the trunk of instantiations that already spill them)
+        const FwdKernelArgs mirror{pts, viewdirs, vd_stride, samples_per_ray, wpk, wh3, sc, raw, save_arg, P, cs, fs, cm};
+        epif.window = late_args(mirror)->cm.lean ? kStoreWindowShut : kStoreWindowOpen;
+    }
     epif.prime();
     // (the feature vector meets the encoded view direction in the views layer: one scale for both)
     trunk_layer(I<1>{}, I<0>{}, I<0>{}, epi7, epif, 7, kLayerFeat, 0.f, m_ev);

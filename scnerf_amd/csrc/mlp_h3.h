@@ -82,6 +82,23 @@ __device__ __forceinline__ float scale_for(float bound) {
 }
 __device__ __forceinline__ float inv_pow2(float s) { return __uint_as_float(0x7f000000u - __float_as_uint(s)); }
 
+// store_written_through_at through a window of `window` bytes behind the wave-uniform base: kStoreWindowOpen is that
+// function; with kStoreWindowShut every lane's offset is out of range, and an out-of-range buffer store is dropped by the
+// address unit -- the instruction stream, its registers and its schedule are those of the storing kernel, and nothing is
+// written.  How the lean workspace (ChunkMaxima::lean) leaves the feature / d feature sections out without a branch in
+// the epilogue slots and without a second instantiation.
+constexpr unsigned kStoreWindowOpen = 0x7fffffffu, kStoreWindowShut = 0u;
+#if defined(SCNERF_SIMT_EMU_BUILD)
+inline void store_written_through_window(global_bytes_rw base, unsigned lane_off, f32x4 v, unsigned window) {
+    if (window != kStoreWindowShut) store_written_through_at(base, lane_off, v);
+}
+#else
+__device__ __forceinline__ void store_written_through_window(global_bytes_rw base, unsigned lane_off, f32x4 v, unsigned window) {
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)window, 0x00020000);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(scn_u32x4, v), rsrc, (int)lane_off, 0, 1 | 2 | 16);
+}
+#endif
+
 // The scale guard (resident_guard.h) on one layer output of the wave's samples: `am` the sample's measured max|z| (both
 // lane halves hold it), `s` the power of two that output was cut at.  Nothing without a record.
 __device__ __forceinline__ void guard_check(const ResidentGuard& g, int guard_layer, float am, float s, bool live, long wave_tile) {

@@ -384,6 +384,7 @@ struct ReduceJob {
     float* dW; float* db;
     int G, BN, BK, n_out, k_out, ldo, col0;
     int block0;                 // first block of this job in the merged grid
+    int overwrite = 0;          // the target is scratch of this call: written whatever ReduceJobs::accumulate says
 };
 constexpr int kMaxJobs = 16;
 struct ReduceJobs { ReduceJob j[kMaxJobs]; int n; int accumulate; };
@@ -400,14 +401,91 @@ __global__ __launch_bounds__(256) void wgrad_reduce_multi_kernel(ReduceJobs jobs
         const int n = (int)(idx / J.k_out), k = (int)(idx % J.k_out);
         float* o = J.dW + (long)n * J.ldo + J.col0 + k;
         const float v = sum_partials(J.part_w + (long)n * J.BK + k, (long)J.BN * J.BK, J.G);
-        *o = jobs.accumulate ? *o + v : v;
+        *o = (jobs.accumulate && !J.overwrite) ? *o + v : v;
         return;
     }
     const long j = idx - nw;
     if (J.db && j < J.n_out) {
         const float v = sum_partials(J.part_b + j, J.BN, J.G);
-        J.db[j] = jobs.accumulate ? J.db[j] + v : v;
+        J.db[j] = (jobs.accumulate && !J.overwrite) ? J.db[j] + v : v;
     }
+}
+
+// ---- the lean group's finishing kernel ---------------------------------------------------------------
+// feature_linear has no activation and feeds the views layer linearly (feature = W_f act7 + b_f, d feature = W_vf^T dZv
+// with W_vf = views_linears.0.weight[:, :256]), so with the sample sums M = sum_p dZv_p act7_p^T [128][256] and
+// s = sum_p dZv_p [128] -- what the views layer's narrow GEMM leaves when its X is act7 --
+//   d views_linears.0.weight[:, :256] = M W_f^T + s b_f^T     (128 x 256, K = 256)
+//   d feature_linear.weight           = W_vf^T M              (256 x 256, K = 128)
+//   d feature_linear.bias             = W_vf^T s,             d views_linears.0.bias = s
+// 33 MFLOP on 0.6 MB of operands instead of a 256 x 256 GEMM over all samples and 4 KB of workspace traffic per sample.
+// One thread per output element, fp64 accumulation in a fixed order (k ascending): deterministic.  A workgroup owns a
+// 16 x 16 tile of one product and stages 16 x 16 operand tiles through LDS so that both operands are read along
+// their contiguous axis; the last workgroup forms the two bias vectors.
+constexpr int kFinTile = 16;
+constexpr int kFinBlocksWF = (256 / kFinTile) * (256 / kFinTile), kFinBlocksWV = (128 / kFinTile) * (256 / kFinTile);
+constexpr int kFinLdsBytes = 2 * kFinTile * (kFinTile + 1) * (int)sizeof(float);
+
+template <int PD>
+__global__ __launch_bounds__(kFinTile * kFinTile) void wgrad_lean_finish_kernel(const float* __restrict__ M, const float* __restrict__ s,
+                                                                                const float* __restrict__ params, float* __restrict__ g,
+                                                                                int accumulate) {
+    using V = scn::mlp::Var<PD>;
+    constexpr int T = kFinTile, LDV = 283;                 // leading dimension of views_linears.0.weight
+    const float* W_f = params + V::kWF;
+    const float* b_f = params + V::kBF;
+    const float* W_vf = params + V::kWV;
+    const int tx = threadIdx.x % T, ty = threadIdx.x / T;
+    float* As = dynamic_lds<float>();                      // [T][T + 1]: As[r][k]
+    float* Bs = As + T * (T + 1);                          // [T][T + 1]: Bs[k][c]
+    auto put = [&](float* o, double v) { *o = accumulate ? *o + (float)v : (float)v; };
+    int b = blockIdx.x;
+    if (b < kFinBlocksWF) {
+        // d W_f[i][j] = sum_n W_vf[n][i] M[n][j]: both operands contiguous along the output axes
+        const int i0 = (b / (256 / T)) * T, j0 = (b % (256 / T)) * T;
+        double acc = 0.0;
+        for (int n0 = 0; n0 < 128; n0 += T) {
+            As[tx * (T + 1) + ty] = W_vf[(long)(n0 + ty) * LDV + i0 + tx];          // As[i][n]
+            Bs[ty * (T + 1) + tx] = M[(n0 + ty) * 256 + j0 + tx];                   // Bs[n][j]
+            block_sync();
+#pragma unroll
+            for (int k = 0; k < T; ++k) acc += (double)As[ty * (T + 1) + k] * (double)Bs[k * (T + 1) + tx];
+            block_sync();
+        }
+        put(g + V::kWF + (i0 + ty) * 256 + j0 + tx, acc);
+        return;
+    }
+    b -= kFinBlocksWF;
+    if (b < kFinBlocksWV) {
+        // d W_v[n][k] = sum_j M[n][j] W_f[k][j] + s[n] b_f[k]: both operands contiguous along the contraction
+        const int n0 = (b / (256 / T)) * T, k0 = (b % (256 / T)) * T;
+        double acc = 0.0;
+        for (int j0 = 0; j0 < 256; j0 += T) {
+            As[ty * (T + 1) + tx] = M[(n0 + ty) * 256 + j0 + tx];                   // As[n][j]
+            Bs[tx * (T + 1) + ty] = W_f[(k0 + ty) * 256 + j0 + tx];                 // Bs[j][k]
+            block_sync();
+#pragma unroll
+            for (int k = 0; k < T; ++k) acc += (double)As[ty * (T + 1) + k] * (double)Bs[k * (T + 1) + tx];
+            block_sync();
+        }
+        acc += (double)s[n0 + ty] * (double)b_f[k0 + tx];
+        put(g + V::kWV + (long)(n0 + ty) * LDV + k0 + tx, acc);
+        return;
+    }
+    // d b_f[i] = sum_n W_vf[n][i] s[n];  d views bias = s
+    const int i = threadIdx.x;
+    double acc = 0.0;
+    for (int n = 0; n < 128; ++n) acc += (double)W_vf[(long)n * LDV + i] * (double)s[n];
+    put(g + V::kBF + i, acc);
+    if (i < 128) g[V::kBV + i] = accumulate ? g[V::kBV + i] + s[i] : s[i];
+}
+
+template <int PD>
+int launch_wgrad_lean_finish(const float* M, const float* s, const float* params, float* g, int accumulate, hipStream_t st) {
+    static_assert(kFinTile * kFinTile == 256, "the bias workgroup has one thread per feature");
+    hipLaunchKernelGGL((wgrad_lean_finish_kernel<PD>), dim3(kFinBlocksWF + kFinBlocksWV + 1), dim3(kFinTile * kFinTile),
+                       kFinLdsBytes, st, M, s, params, g, accumulate);
+    return scn_launch_status();
 }
 
 template <int WN, int WK, bool FAST>
@@ -641,13 +719,25 @@ long long vecmat_ws_floats(long long n_chunks) { return (257 * n_chunks + 3) / 4
 // eight times as many samples -- and the partial slabs (256 KB each) shrink from 0.5 GB to 67 MB written and re-read.
 int big_chunks(int n_chunks) { return (n_chunks >= 8 && n_chunks % 8 == 0) ? n_chunks / 8 : n_chunks; }
 
+// the partial slabs of every GEMM of a pass (scnerf_nerf_wgrad_workspace_floats); behind them the lean group's M and s
+long long partial_floats(long long G) {
+    auto blk = [&](long long bn, long long bk) { return G * (bn * bk + bn); };
+    return vecmat_ws_floats(G) + 9 * blk(256, 256) + 2 * blk(256, 128) + blk(128, 256) + blk(128, 64) + blk(64, 128);
+}
+long long lean_scratch_offset(int n_chunks) { return partial_floats(n_chunks); }
+constexpr long long kLeanScratchFloats = 128 * 256 + 128;
+
 template <int PD>
 int nerf_wgrad(const float* save, const float* grads, const float* d_raw, long long P, int n_chunks,
                float* workspace, float* g, int accumulate, void* stream, const float* amax_x = nullptr,
                const float* amax_z = nullptr, const float* scales = nullptr, hipEvent_t ev_before = nullptr,
-               hipEvent_t ev_after = nullptr) {
+               hipEvent_t ev_after = nullptr, const float* lean_params = nullptr) {
+    // lean_params (the flat parameter buffer of the network that ran the pass): the LEAN group for workspaces whose
+    // feature / d feature sections were not stored -- no feature_linear job (seven in the big launch, same chunking: the
+    // other gradients stay bit-identical), the views layer's narrow GEMM on act7 into scratch, wgrad_lean_finish_kernel
     using namespace scn::mlp;
     using V = Var<PD>;
+    const bool lean = lean_params != nullptr;
     const long long Ppad = scn::mlp::padded_samples(P);
     auto S = [&](int sec) { return save + (long long)sec * Ppad; };
     auto G = [&](int sec) { return grads + (long long)sec * Ppad; };
@@ -666,6 +756,7 @@ int nerf_wgrad(const float* save, const float* grads, const float* d_raw, long l
     // the narrow GEMMs on three fp16 products: rows 8 .. 10 of the dZ maxima are dZ of the views layer, dZ of layer 0
     // and max(1, |point|) >= the encoded point (mlp_bwd_h3_kernel.h); the feature is bounded through its layer
     const bool half_narrow = amax_x && amax_z && scales && wgrad_arithmetic() == 1;
+    SCN_RETURN_IF(lean && !half_narrow, SCN_EINVAL);     // (a lean workspace has no feature sections for the full group)
     const long coarse_chunk = (long)scnerf_wgrad_chunk_samples(P, nb);
     auto zrow = [&](int r) { return wgnh::Bound{amax_z + (long)r * nb, nullptr, nullptr}; };
     const NarrowScales ns_l0{zrow(9), zrow(10), nb, coarse_chunk};
@@ -708,7 +799,9 @@ int nerf_wgrad(const float* save, const float* grads, const float* d_raw, long l
         pair.n = 0;                  // (flushed: a later GEMM of the pair's shape starts a new pair instead of re-launching this one)
     }
     // feature_linear; alpha_linear (one output row) = d sigma^T . act7 with d sigma = d_raw[:, 3]
-    SCN_WG(G(kGradDfeat), 256, 256, 256, 1, act(7), 256, 256, 256, 1, P, nb, ws, g + V::kWF, 256, 0, g + V::kBF)
+    if (!lean) {
+        SCN_WG(G(kGradDfeat), 256, 256, 256, 1, act(7), 256, 256, 256, 1, P, nb, ws, g + V::kWF, 256, 0, g + V::kBF)
+    }
     {
         // (its partials [G][257] are finished by the merged reduction below: the 256 sums and the bias sum as two jobs)
         hipLaunchKernelGGL(vecmat_kernel, dim3(n_chunks), dim3(kThreads), 0, st, act(7), d_raw + 3, 4, (long)P, (long)(Ppad / 32), workspace);
@@ -730,7 +823,9 @@ int nerf_wgrad(const float* save, const float* grads, const float* d_raw, long l
         float* part_w = ws;
         float* part_b = part_w + (long)Gv * 128 * 256;
         float* part_w2 = part_b + (long)Gv * 128;
-        wgnh::Args t{G(kGradDzv), S(kSaveFeat), part_w, part_b, (long)P, (long)Ppad, chunk, ns_views.a, ns_views.b, nb, coarse_chunk,
+        // (lean: X = act7, bounded by its own maxima -- row 7 of the X table -- instead of the feature behind it)
+        wgnh::Args t{G(kGradDzv), lean ? act(7) : S(kSaveFeat), part_w, part_b, (long)P, (long)Ppad, chunk, ns_views.a,
+                     lean ? wgnh::Bound{amax_x + 7L * nb, nullptr, nullptr} : ns_views.b, nb, coarse_chunk,
                      S(kSaveEviews), part_w2, zrow(11)};
         SCN_LDS_OPT_IN((wgnh::wgrad_half_narrow_kernel<128, 256, false, 32>), wgnh::kLdsBytes);
         hipLaunchKernelGGL((wgnh::wgrad_half_narrow_kernel<128, 256, false, 32>), dim3(Gv), dim3(wgnh::kThreads), wgnh::kLdsBytes, st, t);
@@ -743,6 +838,10 @@ int nerf_wgrad(const float* save, const float* grads, const float* d_raw, long l
         J2.part_w = part_w2; J2.part_b = nullptr; J2.dW = g + V::kWV; J2.db = nullptr;
         J2.G = Gv; J2.BN = 128; J2.BK = 32; J2.n_out = 128; J2.k_out = 27; J2.ldo = 283; J2.col0 = 256; J2.block0 = 0;
         ws += (long)Gv * (128 * 256 + 128 + 128 * 32);
+        if (lean) {                  // M and s: scratch behind everything else, finished below
+            J1.dW = workspace + lean_scratch_offset(n_chunks); J1.db = J1.dW + 128 * 256;
+            J1.ldo = 256; J1.overwrite = 1;
+        }
     } else {
         SCN_WG(G(kGradDzv), 128, 128, 128, 1, S(kSaveFeat), 256, 256, 256, 1, P, n_chunks, ws, g + V::kWV, 283, 0, g + V::kBV)
         SCN_WG(G(kGradDzv), 128, 128, 128, 1, S(kSaveEviews), 32, 32, 27, 0, P, n_chunks, ws, g + V::kWV, 283, 256, nullptr)
@@ -777,7 +876,14 @@ int nerf_wgrad(const float* save, const float* grads, const float* d_raw, long l
         blocks += (int)scn_ceil_div(total, 256);
     }
     hipLaunchKernelGGL(wgrad_reduce_multi_kernel, dim3(blocks), dim3(256), 0, st, jobs);
-    return scn_launch_status();
+    rc = scn_launch_status();
+    if (rc != 0 || !lean) return rc;
+    if constexpr (PD == 3) {
+        const float* M = workspace + lean_scratch_offset(n_chunks);
+        return launch_wgrad_lean_finish<3>(M, M + 128 * 256, lean_params, g, accumulate, st);
+    } else {
+        return SCN_EINVAL;           // (the lean group exists for the standard network)
+    }
 }
 }  // namespace
 
@@ -813,6 +919,23 @@ extern "C" int scnerf_nerf_wgrad_h3(int pt_dims, const float* save, const float*
     SCN_RETURN_IF(pt_dims != 3 && pt_dims != 4, SCN_EINVAL);
     if (pt_dims == 3) return nerf_wgrad<3>(save, grads, d_raw, n_samples, n_chunks, workspace, flat_grad, accumulate, stream, amax_x, amax_z, scales, (hipEvent_t)ev_before, (hipEvent_t)ev_after);
     return nerf_wgrad<4>(save, grads, d_raw, n_samples, n_chunks, workspace, flat_grad, accumulate, stream, amax_x, amax_z, scales, (hipEvent_t)ev_before, (hipEvent_t)ev_after);
+}
+
+// the lean group (include/scnerf_hip.h): standard network, all three tables, the half arithmetic
+extern "C" int scnerf_nerf_wgrad_h3_lean(int pt_dims, const float* save, const float* grads, const float* d_raw,
+                                         long long n_samples, int n_chunks, float* workspace, float* flat_grad,
+                                         int accumulate, const float* amax_x, const float* amax_z, const float* scales,
+                                         const float* flat_params, void* ev_before, void* ev_after, void* stream) {
+    SCN_RETURN_IF(!save || !grads || !d_raw || !workspace || !flat_grad || n_samples < 1 || n_chunks < 1, SCN_EINVAL);
+    SCN_RETURN_IF(pt_dims != 3 || !amax_x || !amax_z || !scales || !flat_params || wgrad_arithmetic() != 1, SCN_EINVAL);
+    return nerf_wgrad<3>(save, grads, d_raw, n_samples, n_chunks, workspace, flat_grad, accumulate, stream, amax_x, amax_z, scales,
+                         (hipEvent_t)ev_before, (hipEvent_t)ev_after, flat_params);
+}
+
+extern "C" int scnerf_wgrad_lean_finish(const float* M, const float* s, const float* flat_params, float* flat_grad,
+                                        int accumulate, void* stream) {
+    SCN_RETURN_IF(!M || !s || !flat_params || !flat_grad, SCN_EINVAL);
+    return launch_wgrad_lean_finish<3>(M, s, flat_params, flat_grad, accumulate, (hipStream_t)stream);
 }
 
 // one narrow GEMM (256 x 64 / 256 x 128 with a row-major X, 128 x 256 with a tile-native X) on three fp16 products with
@@ -860,7 +983,6 @@ extern "C" int scnerf_wgrad256_half(const float* dz_tiled, const float* x_tiled,
 long long scnerf_nerf_wgrad_workspace_floats(int n_chunks) {
     // every GEMM keeps its partials until the single reduction launch: 9 x (256 x 256), 2 x (256 x 128 | 64),
     // (128 x 256), (128 x 64), (64 x 128) blocks + the vecmat partials
-    const long long G = n_chunks;
-    auto blk = [&](long long bn, long long bk) { return G * (bn * bk + bn); };
-    return vecmat_ws_floats(G) + 9 * blk(256, 256) + 2 * blk(256, 128) + blk(128, 256) + blk(128, 64) + blk(64, 128);
+    // + the lean group's scratch (M [128][256], s [128])
+    return partial_floats(n_chunks) + kLeanScratchFloats;
 }

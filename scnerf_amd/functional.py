@@ -86,6 +86,9 @@ class RenderRaysFunction(torch.autograd.Function):
         resident = isinstance(pl_c, ops.ResidentWeights)
         # (resident kernels, training: they leave the chunk maxima the fp16 weight-gradient GEMMs scale by)
         mx_c = ops.ChunkMaxima(n * sc, dev) if (train and resident) else None
+        # the lean workspace (ops.lean_workspace): decided ONCE here -- the data gradients and the weight-gradient group of
+        # this call follow the decision, whatever the switches say by then
+        lean = bool(ops.lean_workspace() and mx_c is not None and ops.wgrad_arithmetic() == "half")
         # (the resident kernels' scale guard, ops.resident_guard: None while it is off)
         # (one record buffer per call, every pass of both stages, forward and data gradients)
         # (forward-only with ops.inference_arithmetic("fast"): the packs say so, and such passes take no record)
@@ -97,16 +100,21 @@ class RenderRaysFunction(torch.autograd.Function):
             # the whole coarse stage -- stratified depths, network, compositing -- is one launch
             z_c, pts_c, raw_c, rgb_c, disp_c, acc_c, w_c, depth_c = ops.coarse_stage_fwd(
                 rays, host_linspace(sc, dev), _c(t_rand), cfg.lindisp, wf_c, save_c, _c(noise_c), cfg.white_bkgd,
-                planes=pl_c, maxima=mx_c, guard=gd_c)
+                planes=pl_c, maxima=mx_c, guard=gd_c, lean=lean)
         else:
             z_c, pts_c = ops.coarse_sample(rays, host_linspace(sc, dev), _c(t_rand), cfg.lindisp)
-            raw_c = ops.mlp_fwd(pts_c, viewdirs, sc, wf_c, save_c, planes=pl_c, maxima=mx_c, guard=gd_c).view(n, sc, 4)
+            raw_c = ops.mlp_fwd(pts_c, viewdirs, sc, wf_c, save_c, planes=pl_c, maxima=mx_c, guard=gd_c, lean=lean).view(n, sc, 4)
             rgb_c, disp_c, acc_c, w_c, depth_c = ops.composite_fwd(raw_c, z_c, rays, _c(noise_c), cfg.white_bkgd)
 
         ctx.cfg, ctx.train, ctx.n = cfg, train, n
         ctx.net_c, ctx.net_f = net_c, net_f
         ctx.n_params_c = len(net_c.ordered_parameters())
         ctx.coarse = (z_c, pts_c, raw_c, _c(noise_c), save_c, mx_c)
+        ctx.lean = lean
+        # (the lean weight-gradient group reads three parameters of the pass's network: a snapshot, as the packed weights
+        #  are -- an in-place update between forward and backward must not reach the backward)
+        ctx.flat_c = flat_c.detach().clone() if lean else None
+        ctx.flat_f = None
         ctx.pl_c = pl_c
         ctx.guards = guards
         ctx.rays = rays
@@ -137,13 +145,14 @@ class RenderRaysFunction(torch.autograd.Function):
             # the whole fine stage -- inverse-cdf sampler, merge, network, compositing -- as one launch (opt-in: measured
             # slower than the three launches below, ops.fused_fine_stage)
             z_f, pts_f, z_s, z_std, _, _, raw_f, rgb_f, disp_f, acc_f, depth_f, _ = ops.fine_stage_fwd(
-                rays, z_c, w_c, u_dev, wf_f, save_f, _c(noise_f), cfg.white_bkgd, pl_f, maxima=mx_f)
+                rays, z_c, w_c, u_dev, wf_f, save_f, _c(noise_f), cfg.white_bkgd, pl_f, maxima=mx_f, lean=lean)
         else:
             z_f, pts_f, z_s, z_std, _, _ = ops.fine_sample(rays, z_c, w_c, u_dev)
-            raw_f = ops.mlp_fwd(pts_f, viewdirs, tot, wf_f, save_f, planes=pl_f, maxima=mx_f, guard=gd_f).view(n, tot, 4)
+            raw_f = ops.mlp_fwd(pts_f, viewdirs, tot, wf_f, save_f, planes=pl_f, maxima=mx_f, guard=gd_f, lean=lean).view(n, tot, 4)
             rgb_f, disp_f, acc_f, _, depth_f = ops.composite_fwd(raw_f, z_f, rays, _c(noise_f), cfg.white_bkgd,
                                                                  want_weights=False)
         ctx.fine = (z_f, pts_f, raw_f, _c(noise_f), save_f, mx_f)
+        ctx.flat_f = (ctx.flat_c if fine_net is net_c else flat_f.detach().clone()) if lean else None
         ctx.pl_f = pl_f
         ctx.wb_f = (ctx.wb_c if fine_net is net_c else ops.pack_weights(flat_f, "bwd")) if train else None
         ctx.mark_non_differentiable(z_std, z_f, z_s)
@@ -151,28 +160,30 @@ class RenderRaysFunction(torch.autograd.Function):
 
     @staticmethod
     def _stage_dgrad(stage, rays, spr, wbk, white_bkgd, g_rgb, g_disp, g_acc, g_depth, g_raw, d_rays, accumulate,
-                     planes=None, guard=None):
+                     planes=None, guard=None, lean=False, flat_params=None):
         """Data gradients of one stage (compositing, network, rays); -> what its weight gradients need.
-        d_rays None: the rays need no gradient -- neither the network's input gradient nor the ray reduction runs."""
+        d_rays None: the rays need no gradient -- neither the network's input gradient nor the ray reduction runs.
+        lean / flat_params: the stage's forward ran lean (ops.lean_workspace) on the network with these parameters."""
         z, pts, raw, noise, save, maxima = stage
         want = d_rays is not None
         d_raw, d_rd = ops.composite_bwd(raw, z, rays, noise, white_bkgd, _c(g_rgb), _c(g_disp), _c(g_acc),
                                         _c(g_depth), _c(g_raw), want_d_rays_d=want)
         grads, d_pts, d_views = ops.mlp_bwd(d_raw, pts, rays[:, 8:11], spr, wbk, save, planes=planes, maxima=maxima,
-                                            input_grad=want, guard=guard)
+                                            input_grad=want, guard=guard, lean=lean)
         if want:
             ops.ray_reduce(d_pts, d_views, z, d_rd, d_rays, accumulate)
-        return save, grads, d_raw, z.shape[0] * spr, maxima
+        return save, grads, d_raw, z.shape[0] * spr, maxima, lean, flat_params
 
     @staticmethod
     def _stage_wgrad(pending, into=None):
         """`into`: the network's attached flat .grad buffer -- the weight gradients are ADDED to it and
         None is returned (nothing for autograd to accumulate); otherwise a fresh flat gradient."""
-        save, grads, d_raw, P, maxima = pending
+        save, grads, d_raw, P, maxima, lean, flat_params = pending
         if into is not None:
-            ops.nerf_wgrad(save, grads, d_raw, P, flat_grad=into, accumulate=True, maxima=maxima)
+            ops.nerf_wgrad(save, grads, d_raw, P, flat_grad=into, accumulate=True, maxima=maxima, lean=lean,
+                           flat_params=flat_params)
             return None
-        return ops.nerf_wgrad(save, grads, d_raw, P, maxima=maxima)
+        return ops.nerf_wgrad(save, grads, d_raw, P, maxima=maxima, lean=lean, flat_params=flat_params)
 
     @staticmethod
     def backward(ctx, g_rgb, g_disp, g_acc, g_depth, g_raw, g_rgb0, g_disp0, g_acc0, g_depth0, *_unused):
@@ -198,14 +209,16 @@ class RenderRaysFunction(torch.autograd.Function):
             if any(g is not None for g in (g_rgb, g_disp, g_acc, g_depth, g_raw)):
                 pend_f = RenderRaysFunction._stage_dgrad(ctx.fine, rays, sc + sf, ctx.wb_f, cfg.white_bkgd,
                                                          g_rgb, g_disp, g_acc, g_depth, g_raw, d_rays, wrote,
-                                                         planes=ctx.pl_f, guard=ctx.guards.get("fine_bwd"))
+                                                         planes=ctx.pl_f, guard=ctx.guards.get("fine_bwd"), lean=ctx.lean,
+                                                         flat_params=ctx.flat_f)
                 wrote = True
             coarse_g = (g_rgb0, g_disp0, g_acc0, g_depth0, None)
         else:
             coarse_g = (g_rgb, g_disp, g_acc, g_depth, g_raw)
         if any(g is not None for g in coarse_g):
             pend_c = RenderRaysFunction._stage_dgrad(ctx.coarse, rays, sc, ctx.wb_c, cfg.white_bkgd,
-                                                     *coarse_g, d_rays, wrote, planes=ctx.pl_c, guard=ctx.guards.get("coarse_bwd"))
+                                                     *coarse_g, d_rays, wrote, planes=ctx.pl_c, guard=ctx.guards.get("coarse_bwd"),
+                                                     lean=ctx.lean, flat_params=ctx.flat_c)
         if pend_f is not None:
             fg_f = RenderRaysFunction._stage_wgrad(pend_f, into=into_f)
         if pend_c is not None:

@@ -571,10 +571,12 @@ _MAC_PER_SAMPLE = {3: 593408, 4: 593408 + 2 * 256 * 21}       # layer 0 and the 
 
 def mlp_fwd(pts: Tensor, viewdirs: Tensor, samples_per_ray: int, wpacked: Tensor,
             save: Optional[Tensor] = None, pd: int = 3, planes: Optional[Tensor] = None,
-            maxima: Optional["ChunkMaxima"] = None, guard: Optional[GuardRecord] = None) -> Tensor:
+            maxima: Optional["ChunkMaxima"] = None, guard: Optional[GuardRecord] = None, lean: bool = False) -> Tensor:
     """pts [P, pd] (pd = 3: x y z; pd = 4: x y z 1/r) -> raw [P, 4] (rgb logits, sigma pre-activation).
     `planes`: the ResidentWeights (pack_resident) -> the resident kernel; None -> the fused fp32-MFMA kernel.
-    `guard`: a GuardRecord (guard_records) for the resident kernel's scale guard; None: no check."""
+    `guard`: a GuardRecord (guard_records) for the resident kernel's scale guard; None: no check.
+    `lean` (resident training pass of the standard network): the feature section of `save` is not written
+    (lean_workspace)."""
     _f(pts, "pts"), _f(wpacked, "wpacked")
     vptr, vstride = _vd(viewdirs)
     lay = ML.layout(pd)
@@ -588,11 +590,13 @@ def mlp_fwd(pts: Tensor, viewdirs: Tensor, samples_per_ray: int, wpacked: Tensor
     if isinstance(planes, ResidentWeights):
         if planes.pd != pd:
             raise ValueError("resident weights of another network variant")
-        return mlp_fwd_resident(pts, viewdirs, samples_per_ray, wpacked, planes, save, maxima, guard)
+        return mlp_fwd_resident(pts, viewdirs, samples_per_ray, wpacked, planes, save, maxima, guard, lean=lean)
     raw = torch.empty((P, 4), dtype=torch.float32, device=pts.device)
     tag = "" if pd == 3 else "/pd4"
     if planes is not None:
         raise TypeError("planes must be a ResidentWeights or None")
+    if lean:
+        raise ValueError("the lean workspace belongs to the resident arithmetic")
     with PROFILE.region("mlp_fwd_kernel%s/P=%d/%s" % (tag, P, "train" if save is not None else "infer"),
                         2 * _MAC_PER_SAMPLE[pd] * P):
         st = _capi.load().scnerf_mlp_fwd(pd, _p(pts), vptr, vstride, int(samples_per_ray), _p(wpacked), _p(raw),
@@ -603,7 +607,7 @@ def mlp_fwd(pts: Tensor, viewdirs: Tensor, samples_per_ray: int, wpacked: Tensor
 
 def mlp_fwd_resident(pts: Tensor, viewdirs: Tensor, samples_per_ray: int, wpacked: Tensor, rw: ResidentWeights,
                      save: Optional[Tensor] = None, maxima: Optional[ChunkMaxima] = None,
-                     guard: Optional[GuardRecord] = None) -> Tensor:
+                     guard: Optional[GuardRecord] = None, lean: bool = False) -> Tensor:
     """mlp_fwd in the resident arithmetic: one launch, three fp16 products per product, activations register-resident
     (csrc/mlp_fwd_h3.hip); save (training) receives the same workspace as mlp_fwd's."""
     _f(pts, "pts"), _f(wpacked, "wpacked")
@@ -618,6 +622,7 @@ def mlp_fwd_resident(pts: Tensor, viewdirs: Tensor, samples_per_ray: int, wpacke
         if save.numel() < lay.save_floats(P):
             raise ValueError("activation workspace too small")
     raw = torch.empty((P, 4), dtype=torch.float32, device=pts.device)
+    _check_lean(lean, pd, save, maxima, rw)
     if rw.fast:
         if save is not None or guard is not None:
             raise ValueError("the one-product arithmetic is forward-only and takes no guard record")
@@ -631,7 +636,9 @@ def mlp_fwd_resident(pts: Tensor, viewdirs: Tensor, samples_per_ray: int, wpacke
         mx = maxima if save is not None else None
         args = (pd, _p(pts), vptr, vstride, int(samples_per_ray), _p(wpacked), _p(rw.fwd), _p(rw.scales), _p(raw), _p(save), P,
                 _p(mx.x) if mx else None, mx.chunks if mx else 0, mx.chunk_samples if mx else 0)
-        if guard is None:
+        if lean:
+            st = _capi.load().scnerf_mlp_fwd_h3_lean(*args, *(guard.args() if guard is not None else _no_guard()), 1, _stream())
+        elif guard is None:
             st = _capi.load().scnerf_mlp_fwd_h3(*args, _stream())
         else:
             st = _capi.load().scnerf_mlp_fwd_h3_guarded(*args, *guard.args(), _stream())
@@ -644,13 +651,19 @@ def mlp_fwd_resident(pts: Tensor, viewdirs: Tensor, samples_per_ray: int, wpacke
     return raw
 
 
+def _check_lean(lean, pd, save, maxima, rw):
+    """a lean pass is a training pass of the standard network that leaves chunk maxima (lean_workspace)"""
+    if lean and (pd != 3 or save is None or maxima is None or rw.fast):
+        raise ValueError("the lean workspace needs a training pass of the standard network with chunk maxima")
+
+
 COARSE_STAGE_SAMPLES = 64        # the fused coarse stage exists for two wave tiles per ray (csrc/mlp_fwd.hip)
 
 
 def coarse_stage_fwd(rays: Tensor, t_vals: Tensor, t_rand: Optional[Tensor], lindisp: bool, wpacked: Tensor,
                      save: Optional[Tensor], noise: Optional[Tensor], white_bkgd: bool, planes: Optional[Tensor] = None,
-                     maxima: Optional["ChunkMaxima"] = None, guard: Optional[GuardRecord] = None):
-    """coarse_sample + mlp_fwd + composite_fwd of the coarse stage as one launch (64 samples per ray):
+                     maxima: Optional["ChunkMaxima"] = None, guard: Optional[GuardRecord] = None, lean: bool = False):
+    """coarse_sample + mlp_fwd + composite_fwd of the coarse stage as one launch (64 samples per ray; `lean`: as mlp_fwd):
     -> (z [n,64], pts [n,64,3], raw [n,64,4], rgb [n,3], disp [n], acc [n], weights [n,64], depth [n])."""
     _f(rays, "rays"), _f(t_vals, "t_vals"), _f(wpacked, "wpacked")
     for name, t_ in (("t_rand", t_rand), ("noise", noise), ("save", save)):
@@ -677,6 +690,7 @@ def coarse_stage_fwd(rays: Tensor, t_vals: Tensor, t_rand: Optional[Tensor], lin
     if isinstance(planes, ResidentWeights):
         if planes.pd != 3:
             raise ValueError("the coarse stage samples 3-D points")
+        _check_lean(lean, 3, save, maxima, planes)
         if planes.fast:
             if save is not None or guard is not None:
                 raise ValueError("the one-product arithmetic is forward-only and takes no guard record")
@@ -693,7 +707,10 @@ def coarse_stage_fwd(rays: Tensor, t_vals: Tensor, t_rand: Optional[Tensor], lin
                     _p(planes.scales), _p(save), _p(noise), int(bool(white_bkgd)), _p(z), _p(pts), _p(raw), _p(rgb), _p(disp),
                     _p(acc), _p(depth), _p(w), n, s, _p(maxima.x) if (maxima and save is not None) else None,
                     maxima.chunks if maxima else 0, maxima.chunk_samples if maxima else 0)
-            if guard is None:
+            if lean:
+                st = _capi.load().scnerf_coarse_stage_fwd_h3_lean(*args, *(guard.args() if guard is not None else _no_guard()),
+                                                                  1, _stream())
+            elif guard is None:
                 st = _capi.load().scnerf_coarse_stage_fwd_h3(*args, _stream())
             else:
                 st = _capi.load().scnerf_coarse_stage_fwd_h3_guarded(*args, *guard.args(), _stream())
@@ -708,6 +725,8 @@ def coarse_stage_fwd(rays: Tensor, t_vals: Tensor, t_rand: Optional[Tensor], lin
         return z, pts, raw, rgb, disp, acc, w, depth
     if planes is not None:
         raise TypeError("planes must be a ResidentWeights or None")
+    if lean:
+        raise ValueError("the lean workspace belongs to the resident arithmetic")
     with PROFILE.region("mlp_fwd_kernel/P=%d/%s" % (P, "train" if save is not None else "infer"), 2 * _MAC_PER_SAMPLE[3] * P):
         st = _capi.load().scnerf_coarse_stage_fwd(_p(rays), rays.shape[1], _p(t_vals), _p(t_rand), int(bool(lindisp)),
                                                   _p(wpacked), _p(save), _p(noise), int(bool(white_bkgd)), _p(z), _p(pts),
@@ -727,6 +746,25 @@ FINE_STAGE_IMPORTANCE = (64, 128, 192)       # the fused fine stage exists for 6
 _FUSED_FINE_STAGE = [os.environ.get("SCNERF_FUSED_FINE_STAGE", "0") not in ("", "0")]
 
 
+# The lean workspace of a training pass (csrc/wgrad.hip): feature_linear has no activation and feeds the
+# views layer linearly, so its weight gradients and the views layer's feature columns follow from ONE views-layer GEMM on
+# act7 -- the resident kernels store neither `feature` nor `d feature`, the big weight-gradient launch runs seven GEMMs
+# instead of eight, a finishing kernel forms three small products in fp64.  Taken by RenderRaysFunction when the pass
+# trains on the resident arithmetic with the half weight-gradient arithmetic and chunk maxima; SCNERF_LEAN_WORKSPACE=0
+# keeps the full workspace and the twelve-GEMM group (one build can be A/B-ed).
+_LEAN_WORKSPACE = [os.environ.get("SCNERF_LEAN_WORKSPACE", "1") not in ("", "0")]
+
+
+def lean_workspace(on: Optional[bool] = None) -> bool:
+    if on is not None:
+        _LEAN_WORKSPACE[0] = bool(on)
+    return _LEAN_WORKSPACE[0]
+
+
+def _no_guard():
+    return (None, None, None)
+
+
 def fused_fine_stage(on: Optional[bool] = None) -> bool:
     if on is not None:
         _FUSED_FINE_STAGE[0] = bool(on)
@@ -735,9 +773,9 @@ def fused_fine_stage(on: Optional[bool] = None) -> bool:
 
 def fine_stage_fwd(rays: Tensor, z_c: Tensor, w_c: Tensor, u: Tensor, wpacked: Tensor, save: Optional[Tensor],
                    noise: Optional[Tensor], white_bkgd: bool, planes: "ResidentWeights", maxima: Optional["ChunkMaxima"] = None,
-                   want_inds=False, want_cdf=False, want_weights=False):
+                   want_inds=False, want_cdf=False, want_weights=False, lean: bool = False):
     """fine_sample + mlp_fwd + composite_fwd of the fine stage as ONE launch (resident arithmetic; 64 coarse samples and
-    N_importance in FINE_STAGE_IMPORTANCE): -> (z_f [n,tot], pts_f [n,tot,3], z_samples [n,sf], z_std [n], inds, cdf,
+    N_importance in FINE_STAGE_IMPORTANCE; `lean`: as mlp_fwd): -> (z_f [n,tot], pts_f [n,tot,3], z_samples [n,sf], z_std [n], inds, cdf,
     raw [n,tot,4], rgb [n,3], disp [n], acc [n], depth [n], weights)."""
     _f(rays, "rays"), _f(z_c, "z_c"), _f(w_c, "w_c"), _f(u, "u"), _f(wpacked, "wpacked")
     for name, t_ in (("noise", noise), ("save", save)):
@@ -773,13 +811,17 @@ def fine_stage_fwd(rays: Tensor, z_c: Tensor, w_c: Tensor, u: Tensor, wpacked: T
     w = torch.empty((n, tot), dtype=torch.float32, device=dev) if want_weights else None
     P = n * tot
     mx = maxima if save is not None else None
+    _check_lean(lean, 3, save, maxima, planes)
     with PROFILE.region("mlp_fwd_h3_kernel<fine stage>/P=%d/%s" % (P, "train" if save is not None else "infer"),
                         2 * _MAC_PER_SAMPLE[3] * P):
-        st = _capi.load().scnerf_fine_stage_fwd_h3(
-            _p(rays), rays.shape[1], _p(z_c), _p(w_c), _p(u), stride, _p(wpacked), _p(planes.fwd), _p(planes.scales), _p(save),
-            _p(noise), int(bool(white_bkgd)), _p(z_f), _p(pts_f), _p(z_s), _p(z_std), _p(inds), _p(cdf), _p(raw), _p(rgb),
-            _p(disp), _p(acc), _p(depth), _p(w), n, sc, sf, _p(mx.x) if mx else None, mx.chunks if mx else 0,
-            mx.chunk_samples if mx else 0, _stream())
+        args = (_p(rays), rays.shape[1], _p(z_c), _p(w_c), _p(u), stride, _p(wpacked), _p(planes.fwd), _p(planes.scales), _p(save),
+                _p(noise), int(bool(white_bkgd)), _p(z_f), _p(pts_f), _p(z_s), _p(z_std), _p(inds), _p(cdf), _p(raw), _p(rgb),
+                _p(disp), _p(acc), _p(depth), _p(w), n, sc, sf, _p(mx.x) if mx else None, mx.chunks if mx else 0,
+                mx.chunk_samples if mx else 0)
+        if lean:
+            st = _capi.load().scnerf_fine_stage_fwd_h3_lean(*args, *_no_guard(), 1, _stream())
+        else:
+            st = _capi.load().scnerf_fine_stage_fwd_h3(*args, _stream())
     _capi.check(st, "scnerf_fine_stage_fwd_h3")
     return z_f, pts_f, z_s, z_std, inds, cdf, raw, rgb, disp, acc, depth, w
 
@@ -790,13 +832,17 @@ def save_workspace(P: int, device, pd: int = 3) -> Tensor:
 
 def mlp_bwd(d_raw: Tensor, pts: Tensor, viewdirs: Tensor, samples_per_ray: int, wpacked_bwd: Tensor,
             save: Tensor, pd: int = 3, planes: Optional[Tensor] = None, maxima: Optional["ChunkMaxima"] = None,
-            input_grad: bool = True, guard: Optional[GuardRecord] = None):
+            input_grad: bool = True, guard: Optional[GuardRecord] = None, lean: bool = False):
     """-> (grads workspace, d_pts [P,pd], d_views [P,3]).  `planes`, `guard`: as mlp_fwd.  input_grad=False: d_pts / d_views
-    are not needed -- the resident kernel skips them and returns None for both (the fp32 kernel computes them anyway)."""
+    are not needed -- the resident kernel skips them and returns None for both (the fp32 kernel computes them anyway).
+    `lean` (the pass whose forward ran lean): the d feature section of the grads workspace is not written."""
     if isinstance(planes, ResidentWeights):
         if planes.pd != pd:
             raise ValueError("resident weights of another network variant")
-        return mlp_bwd_resident(d_raw, pts, viewdirs, samples_per_ray, wpacked_bwd, planes, save, maxima, input_grad, guard)
+        return mlp_bwd_resident(d_raw, pts, viewdirs, samples_per_ray, wpacked_bwd, planes, save, maxima, input_grad, guard,
+                                lean=lean)
+    if lean:
+        raise ValueError("the lean workspace belongs to the resident arithmetic")
     _f(d_raw, "d_raw"), _f(pts, "pts"), _f(wpacked_bwd, "wpacked_bwd"), _f(save, "save")
     vptr, vstride = _vd(viewdirs)
     lay = ML.layout(pd)
@@ -818,7 +864,7 @@ def mlp_bwd(d_raw: Tensor, pts: Tensor, viewdirs: Tensor, samples_per_ray: int, 
 
 def mlp_bwd_resident(d_raw: Tensor, pts: Tensor, viewdirs: Tensor, samples_per_ray: int, wpacked_bwd: Tensor,
                      rw: ResidentWeights, save: Tensor, maxima: Optional[ChunkMaxima] = None, input_grad: bool = True,
-                     guard: Optional[GuardRecord] = None):
+                     guard: Optional[GuardRecord] = None, lean: bool = False):
     """mlp_bwd in the resident arithmetic (csrc/mlp_bwd_h3.hip): one launch -> (grads workspace, d_pts, d_views);
     input_grad=False: the instantiation without the input gradient, d_pts = d_views = None."""
     _f(d_raw, "d_raw"), _f(pts, "pts"), _f(wpacked_bwd, "wpacked_bwd"), _f(save, "save")
@@ -828,6 +874,7 @@ def mlp_bwd_resident(d_raw: Tensor, pts: Tensor, viewdirs: Tensor, samples_per_r
     P = pts.numel() // pd
     if wpacked_bwd.numel() != lay.bwd_total:
         raise ValueError("wpacked_bwd has the wrong size")
+    _check_lean(lean, pd, save, maxima, rw)
     dev = pts.device
     grads = torch.empty(ML.grad_floats(P), dtype=torch.float32, device=dev)
     d_pts = torch.empty((P, pd), dtype=torch.float32, device=dev) if input_grad else None
@@ -838,7 +885,9 @@ def mlp_bwd_resident(d_raw: Tensor, pts: Tensor, viewdirs: Tensor, samples_per_r
         args = (pd, _p(d_raw), _p(pts), vptr, vstride, int(samples_per_ray), _p(wpacked_bwd), _p(rw.bwd), _p(rw.scales),
                 _p(save), _p(grads), _p(d_pts), _p(d_views), P, _p(maxima.z) if maxima else None,
                 maxima.chunks if maxima else 0, maxima.chunk_samples if maxima else 0)
-        if guard is None:
+        if lean:
+            st = _capi.load().scnerf_mlp_bwd_h3_lean(*args, *(guard.args() if guard is not None else _no_guard()), 1, _stream())
+        elif guard is None:
             st = _capi.load().scnerf_mlp_bwd_h3(*args, _stream())
         else:
             st = _capi.load().scnerf_mlp_bwd_h3_guarded(*args, *guard.args(), _stream())
@@ -873,9 +922,13 @@ def wgrad_arithmetic(mode: Optional[str] = None) -> str:
 
 
 def nerf_wgrad(save: Tensor, grads: Tensor, d_raw: Tensor, P: int, flat_grad: Optional[Tensor] = None,
-               pd: int = 3, accumulate: bool = False, maxima: Optional[ChunkMaxima] = None) -> Tensor:
+               pd: int = 3, accumulate: bool = False, maxima: Optional[ChunkMaxima] = None, lean: bool = False,
+               flat_params: Optional[Tensor] = None) -> Tensor:
     """All parameter gradients of one network -> flat buffer (mlp_layout.Layout parameter order);
-    `accumulate`: add to `flat_grad` instead of overwriting it."""
+    `accumulate`: add to `flat_grad` instead of overwriting it.
+    `lean`: the workspaces come from lean passes (lean_workspace: no feature / d feature sections) -- the lean group, which
+    needs `flat_params`, the flat parameter buffer of the network that ran the pass, the chunk maxima of both resident
+    kernels and the half arithmetic; without any of them it raises (a lean workspace must never reach the full group)."""
     lib = _capi.load()
     chunks = wgrad_chunks(P)
     key = (chunks, str(save.device))
@@ -891,21 +944,38 @@ def nerf_wgrad(save: Tensor, grads: Tensor, d_raw: Tensor, P: int, flat_grad: Op
     # in `scales`): a half-filled table would scale one operand by 2^126
     if maxima is not None and maxima.scales is None:
         maxima = None
-    with PROFILE.region("wgrad(12 GEMMs + reduces)%s/P=%d" % (tag, P), 2 * _MAC_PER_SAMPLE[pd] * P, group=True):
+    if lean:
+        if pd != 3 or maxima is None or flat_params is None:
+            raise ValueError("the lean weight-gradient group needs the standard network, the chunk maxima of both resident "
+                             "kernels and flat_params")
+        if wgrad_arithmetic() != "half":
+            raise RuntimeError("the weight-gradient arithmetic was switched away from \"half\" after a lean forward pass: its "
+                               "workspace has no feature sections for the full group")
+        _f(flat_params, "flat_params")
+        if flat_params.numel() != ML.layout(pd).n_params:
+            raise ValueError("flat_params of another network")
+    group = "wgrad(11 GEMMs + reduces + finish, lean)" if lean else "wgrad(12 GEMMs + reduces)"
+    with PROFILE.region("%s%s/P=%d" % (group, tag, P), 2 * _MAC_PER_SAMPLE[pd] * P, group=True):
         ev = (None, None)
         if PROFILE.enabled:
             # the dominant launch inside this C call -- the eight 256 x 256 GEMMs -- between two events the call records
             mode = wgrad_arithmetic()
             if mode == "half" and maxima is None:
                 mode = "fp32"
-            inner = PROFILE.raw_pair("wgrad256_kernel<8 GEMMs, %s>%s/P=%d" % (mode, tag, P), 8 * 2 * 256 * 256 * P)
+            big = 7 if lean else 8
+            inner = PROFILE.raw_pair("wgrad256_kernel<%d GEMMs, %s>%s/P=%d" % (big, mode, tag, P), big * 2 * 256 * 256 * P)
             ev = (inner[0].cuda_event, inner[1].cuda_event)
         if maxima is not None and maxima.chunks != lib.scnerf_wgrad256_chunks(chunks):
             raise ValueError("chunk maxima of another chunking")
-        st = lib.scnerf_nerf_wgrad_h3(pd, _p(save), _p(grads), _p(d_raw), P, chunks, _p(_wgrad_ws[key]),
-                                      _p(flat_grad), int(bool(accumulate)), _p(maxima.x) if maxima else None,
-                                      _p(maxima.z) if maxima else None, _p(maxima.scales) if maxima else None, ev[0], ev[1],
-                                      _stream())
+        if lean:
+            st = lib.scnerf_nerf_wgrad_h3_lean(pd, _p(save), _p(grads), _p(d_raw), P, chunks, _p(_wgrad_ws[key]),
+                                               _p(flat_grad), int(bool(accumulate)), _p(maxima.x), _p(maxima.z),
+                                               _p(maxima.scales), _p(flat_params), ev[0], ev[1], _stream())
+        else:
+            st = lib.scnerf_nerf_wgrad_h3(pd, _p(save), _p(grads), _p(d_raw), P, chunks, _p(_wgrad_ws[key]),
+                                          _p(flat_grad), int(bool(accumulate)), _p(maxima.x) if maxima else None,
+                                          _p(maxima.z) if maxima else None, _p(maxima.scales) if maxima else None, ev[0], ev[1],
+                                          _stream())
     _capi.check(st, "scnerf_nerf_wgrad")
     return flat_grad
 
