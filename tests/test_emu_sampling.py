@@ -99,7 +99,8 @@ def test_coarse_sample_bit_exact(lindisp, perturb):
     np.testing.assert_array_equal(pts, po.numpy())
 
 
-@pytest.mark.parametrize("sc,sf,det", [(64, 128, False), (64, 64, False), (64, 128, True), (16, 24, False), (64, 200, False), (64, 192, False)])
+@pytest.mark.parametrize("sc,sf,det", [(64, 128, False), (64, 64, False), (64, 128, True), (16, 24, False), (64, 200, False), (64, 192, False),
+                                       (40, 33, False), (40, 33, True)])
 def test_fine_sample_bit_exact(sc, sf, det):
     n = 10
     g = torch.Generator().manual_seed(sc + sf)

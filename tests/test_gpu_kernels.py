@@ -50,9 +50,13 @@ def test_searchsorted_matches_numpy(ops, side, Ba, Bv, A, V):
         np.testing.assert_array_equal(out[r], np.searchsorted(a[0 if Ba == 1 else r], v[0 if Bv == 1 else r], side=side))
 
 
-@pytest.mark.parametrize("lindisp,perturb", [(0, 0), (0, 1), (1, 1)])
-def test_coarse_sample_bit_exact(ops, lindisp, perturb):
-    n, s = 1001, 64
+@pytest.mark.parametrize("lindisp,perturb,n,s",
+                         [pytest.param(ld, pt, 1001, 64, id="%d-%d" % (ld, pt)) for ld, pt in [(0, 0), (0, 1), (1, 1)]]
+                         # sample counts other than 64: the three-launch coarse stage of every such run (fewer than one
+                         # pass of 64 lanes, a partial pass, more than one pass)
+                         + [pytest.param(ld, pt, 37, s_, id="%d-%d-37rays-s%d" % (ld, pt, s_))
+                            for s_ in (16, 40, 96) for ld, pt in [(0, 0), (0, 1), (1, 1)]])
+def test_coarse_sample_bit_exact(ops, lindisp, perturb, n, s):
     rays = synth.ray_batch(n, seed=5, lindisp=bool(lindisp))
     t_rand = synth.render_randoms(n, s, 0, seed=6)["t_rand"]
     t_vals = torch.linspace(0.0, 1.0, steps=s)
@@ -63,7 +67,10 @@ def test_coarse_sample_bit_exact(ops, lindisp, perturb):
     np.testing.assert_array_equal(pts.cpu().numpy(), po.numpy())
 
 
-@pytest.mark.parametrize("sc,sf,det,n", [(64, 128, False, 1023), (64, 64, False, 100), (64, 128, True, 100)])
+@pytest.mark.parametrize("sc,sf,det,n", [(64, 128, False, 1023), (64, 64, False, 100), (64, 128, True, 100),
+                                           # odd sf: the rows of u, z_samples and z_f are not 16-byte aligned; sc != 64;
+                                           # sc + sf > 256: the pairwise merge walk
+                                           (40, 33, False, 37), (40, 33, True, 37), (16, 16, False, 37), (64, 200, False, 9)])
 def test_fine_sample_bit_exact(ops, sc, sf, det, n):
     g = torch.Generator().manual_seed(sc + sf)
     rays = synth.ray_batch(n, seed=7)

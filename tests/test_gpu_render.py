@@ -31,23 +31,8 @@ def R():
     return dict(render=render, create_nerf=create_nerf, helpers=run_nerf_helpers, ops=ops)
 
 
-def net_params(seed, kind="xavier"):
-    """`kind` (tests/trained_weights.py): "xavier" = the reference's initialisation; "trained" = the coarse (seed 0) / fine
-    (seed 1) network after 5000 steps on the procedural scene"""
-    from tests import trained_weights as TW
-    return TW.weights(kind, seed, which="coarse" if seed == 0 else "fine")
-
-
-def make_net(R, seed, kind="xavier"):
-    net = R["helpers"].NeRF(D=8, W=256, input_ch=63, input_ch_views=27, output_ch=5, skips=[4], use_viewdirs=True)
-    net.load_state_dict(net_params(seed, kind))
-    return net.cuda()
-
-
-def make_query(R):
-    e, _ = R["helpers"].get_embedder(10, 0)
-    ed, _ = R["helpers"].get_embedder(4, 0)
-    return R["create_nerf"].FusedNetworkQuery(e, ed)
+from tests.render_step_case import make_net, make_query, net_params      # noqa: E402,F401  (shared with the interpreter twin)
+from tests.render_step_case import kernel_gates as _kernel_gates, render_node as _render_node      # noqa: E402,F401
 
 
 def rel_err(a, b):
@@ -206,31 +191,6 @@ def test_fine_stage_strict(R):
     np.testing.assert_allclose(disp.cpu().numpy(), o["disp_map"].numpy(), rtol=1e-4, atol=1e-4)
 
 
-def _render_node(tensor):
-    """the RenderRaysFunction node behind an output of render_rays (its ctx: .coarse / .fine hold the activation workspaces)"""
-    seen, todo = set(), [tensor.grad_fn]
-    while todo:
-        fn = todo.pop()
-        if fn is None or fn in seen:
-            continue
-        seen.add(fn)
-        if "RenderRaysFunction" in type(fn).__name__:
-            return fn
-        todo.extend(f for f, _ in fn.next_functions)
-    raise AssertionError("no RenderRaysFunction node behind this tensor")
-
-
-def _kernel_gates(save, P, pd=3):
-    """the ReLU decisions the training forward took, from the bit masks behind its activation workspace:
-    -> 8 x bool [P, 256] (trunk) + bool [P, 128] (views layer)"""
-    from scnerf_amd import mlp_layout as ML
-    from tests.test_gpu_kernels import _gates_from_masks
-    lay = ML.layout(pd)
-    _, total = ML.section_offsets(lay.save_sections, P)
-    masks = save[total:].cpu().numpy().view(np.uint32).reshape(9, ML.padded_samples(P) // 32, 64, 4)
-    return [torch.from_numpy(_gates_from_masks(masks[l], P, 8 if l < 8 else 4)) for l in range(9)]
-
-
 @pytest.mark.parametrize("n,kind,mode,data_rays", [(256, "xavier", None, False), (4096, "xavier", None, False),
                                                    (4096, "trained", None, False), (4096, "trained", "fp32", False),
                                                    (256, "xavier", None, True), (4096, "trained", None, True)],
@@ -262,65 +222,85 @@ def test_training_gradients_with_both_discontinuities_aligned(R, n, kind, mode, 
         R["ops"].wgrad_arithmetic(saved[1])
 
 
-def _aligned_gradients_case(R, n, kind, mode, host_linspace, data_rays=False):
-    sc, sf = 64, 128                       # (4096 rays: the headline batch -- 8.6e8 ReLU decisions taken from the bit masks)
-    net_c, net_f = make_net(R, 0, kind), make_net(R, 1, kind)
-    rays = synth.ray_batch(n, seed=11)
-    rnd = synth.render_randoms(n, sc, sf, seed=12)
-    rnd_d = {k: v.cuda() for k, v in rnd.items()}
-    target = torch.rand(n, 3, generator=torch.Generator().manual_seed(13))
-    rays_d = rays.cuda().requires_grad_(not data_rays)
-    ret = R["render"].render_rays(rays_d, net_c, make_query(R), sc, retraw=True, perturb=1.0, N_importance=sf,
-                                  network_fine=net_f, raw_noise_std=1.0, _randoms=rnd_d)
-    node = _render_node(ret["rgb_map"])
-    gates_c, gates_f = _kernel_gates(node.coarse[4], n * sc), _kernel_gates(node.fine[4], n * (sc + sf))
-    loss = torch.mean((ret["rgb_map"] - target.cuda()) ** 2) + torch.mean((ret["rgb0"] - target.cuda()) ** 2)
-    loss.backward()
-    st = PA.gpu_sampling_state(R["ops"], host_linspace, rays.cuda(), net_c, rnd_d["t_rand"], rnd_d["u"], rnd_d["noise_c"], sc)
-    assert torch.equal(st["rgb0"], ret["rgb0"].detach())                # the re-run IS the coarse stage of the run above
-    pc = {k: v.clone().requires_grad_(True) for k, v in net_params(0, kind).items()}
-    pf = {k: v.clone().requires_grad_(True) for k, v in net_params(1, kind).items()}
-    rays_o = rays.clone().requires_grad_(True)
-    kw = dict(rowsum="aten", z_samples=st["z_s"].cpu())
-    rec = {}
-    with torch.no_grad():                                               # the oracle's own decisions, for the count
-        own = O.render_rays(rays, pc, pf, sc, sf, rnd["t_rand"], rnd["u"], rnd["noise_c"], rnd["noise_f"], record_gates=rec, **kw)
-    flips = sum(int((a != b).sum()) for a, b in zip(rec["coarse"] + rec["fine"], gates_c + gates_f))
-    n_gates = sum(a.numel() for a in rec["coarse"] + rec["fine"])
-    assert flips <= 1e-5 * n_gates, (flips, n_gates)                    # a handful of 1e8 (measured: see the report)
-    o = O.render_rays(rays_o, pc, pf, sc, sf, rnd["t_rand"], rnd["u"], rnd["noise_c"], rnd["noise_f"],
-                      gates_coarse=gates_c, gates_fine=gates_f, **kw)
-    np.testing.assert_array_equal(o["z_fine"].detach().numpy(), st["z_f"].cpu().numpy())   # identical merged depths
-    # imposing the gates moves nothing visible: a flipped unit's pre-activation is a rounding from zero
-    assert float((o["raw"].detach() - own["raw"]).abs().max()) <= 1e-5
-    loss_o = torch.mean((o["rgb_map"] - target) ** 2) + torch.mean((o["rgb0"] - target) ** 2)
-    loss_o.backward()
-    for name in ("rgb_map", "acc_map", "rgb0", "acc0"):                                      # every ray, no attribution needed
-        np.testing.assert_allclose(ret[name].detach().cpu().numpy(), o[name].detach().numpy(), rtol=0, atol=1e-4, err_msg=name)
-    np.testing.assert_allclose(float(loss.detach()), float(loss_o.detach()), rtol=2e-6)
-    rep = {}
-    for tag, net, p in (("coarse", net_c, pc), ("fine", net_f, pf)):
-        for pn, prm in net.named_parameters():
-            ref = p[pn].grad.numpy()
-            e = np.abs(prm.grad.cpu().numpy() - ref).reshape(-1) / (np.abs(ref).max() + 1e-30)
-            # (the 99.9 % quantile of a tensor with fewer than 2000 entries IS its largest entries: only the max bound applies)
-            rep[tag + "/" + pn] = [float(np.quantile(e, 0.999)) if e.size >= 2000 else 0.0, float(e.max())]
-    worst = max(rep, key=lambda k_: rep[k_][1])
-    entry = dict(relu_decisions=n_gates, relu_decisions_differing_from_the_oracles_own=flips,
-                 worst_q999=max(v[0] for v in rep.values()), worst_max=rep[worst][1], worst_parameter=worst)
-    if data_rays:
-        assert rays_d.grad is None
-    else:
-        cols = [0, 1, 2, 3, 4, 5, 8, 9, 10]
-        ge = np.abs(rays_d.grad[:, cols].cpu().numpy() - rays_o.grad[:, cols].numpy()).max(1) / np.abs(rays_o.grad.numpy()).max()
-        entry["d_ray_batch_worst_ray"] = float(ge.max())
-    REPORT["training_gradients_discontinuities_aligned_%dx(64+128)%s%s%s" % (
-        n, "" if kind == "xavier" else "_%s_weights" % kind, "" if mode is None else "/" + mode,
-        "_data_rays" if data_rays else "")] = entry
-    for key, (q999, mx) in rep.items():
-        assert q999 <= 2e-5 and mx <= 1e-4, (key, q999, mx)
-    if not data_rays:
-        assert ge.max() <= 1e-4, float(ge.max())
+def _aligned_gradients_case(R, n, kind, mode, host_linspace, data_rays=False, **options):
+    """(the body: tests/render_step_case.py, shared with tests/test_emu_render_step.py; 4096 rays x (64 + 128): the headline
+    batch -- 8.6e8 ReLU decisions taken from the bit masks)"""
+    from tests.render_step_case import aligned_gradients_case
+    return aligned_gradients_case(R, n, kind, mode, host_linspace, data_rays, **options)
+
+
+# sc, sf, arithmetic (None: the one in force), rays, options
+GENERAL_SIZE_CASES = [
+    (16, 16, None, 37, {}),
+    (40, 33, None, 37, {}),                                   # 73 samples per ray: rays straddle 128-sample blocks, odd P
+    (40, 33, "fp32", 37, {}),
+    (40, 33, None, 37, dict(data_rays=True)),
+    (40, 33, None, 37, dict(lindisp=True, white_bkgd=True)),
+    (40, 33, None, 37, dict(perturb=0.0)),                    # no t_rand, the shared deterministic u row
+    (64, 200, None, 9, {}),                                   # 264: the fused coarse stage, the three-launch fine stage
+    (96, 0, None, 37, {}),                                    # no fine stage
+    (40, 33, None, 37, dict(shared_net=True)),
+    (40, 33, None, 37, dict(shared_net=True, attached=True)),
+    (64, 128, None, 37, dict(shared_net=True)),
+]
+
+
+def _general_case_id(c):
+    sc, sf, mode, n, opt = c
+    return "%dx(%d+%d)%s%s" % (n, sc, sf, "" if mode is None else "_" + mode,
+                               "".join("_%s" % k if v is True else "_%s%g" % (k, v) for k, v in opt.items()))
+
+
+@pytest.mark.parametrize("case", GENERAL_SIZE_CASES, ids=_general_case_id)
+def test_training_gradients_aligned_at_general_sample_counts(R, case):
+    """test_training_gradients_with_both_discontinuities_aligned -- the same body, the same bounds -- at sample counts that
+    are no multiple of 64 (the three-launch coarse stage, rays that straddle the 128-sample blocks and the waves, an odd
+    n * samples_per_ray for the chunk maxima, the half weight-gradient group and the lean workspace), without a fine stage,
+    and with ONE network for both stages (network_fine=None, reference render.py:279: shared packs and backward tables, the
+    summed gradient, the attached flat .grad buffer accumulated into twice).  37 / 9 rays, xavier weights; the report
+    entry of each case is keyed by its sizes and options."""
+    from scnerf_amd.functional import host_linspace
+    sc, sf, mode, n, opt = case
+    saved = (R["ops"].mlp_arithmetic(), R["ops"].wgrad_arithmetic())
+    if mode is not None:
+        R["ops"].mlp_arithmetic(mode)
+        R["ops"].wgrad_arithmetic(mode)
+    try:
+        print("\n%s: %s" % (_general_case_id(case), json.dumps(
+            _aligned_gradients_case(R, n, "xavier", mode, host_linspace, sc=sc, sf=sf, **opt))))
+    finally:
+        R["ops"].mlp_arithmetic(saved[0])
+        R["ops"].wgrad_arithmetic(saved[1])
+
+
+def test_general_sample_count_step_is_bit_identical_under_the_scale_guard(R):
+    """37 rays x (40 + 33) -- ceil(P / 128) blocks with a ragged last one: a training step under ops.resident_guard("fallback")
+    and one under "strict" return the outputs and gradients of the step with the guard off, bit for bit, and "strict" does
+    not raise (xavier weights trip nothing; the guarded entry points promise identical outputs)."""
+    ops = R["ops"]
+    n, sc, sf = 37, 40, 33
+    rays = synth.ray_batch(n, seed=11).cuda()
+    rnd = {k: v.cuda() for k, v in synth.render_randoms(n, sc, sf, seed=12).items()}
+    target = torch.rand(n, 3, generator=torch.Generator().manual_seed(13)).cuda()
+    saved = (ops.resident_guard(), ops.mlp_arithmetic())
+    results = {}
+    try:
+        ops.mlp_arithmetic("resident")
+        for guard in ("off", "fallback", "strict"):
+            ops.resident_guard(guard)
+            net_c, net_f = make_net(R, 0), make_net(R, 1)
+            rd = rays.clone().requires_grad_(True)
+            ret = R["render"].render_rays(rd, net_c, make_query(R), sc, retraw=True, perturb=1.0, N_importance=sf,
+                                          network_fine=net_f, raw_noise_std=1.0, _randoms=rnd)
+            (torch.mean((ret["rgb_map"] - target) ** 2) + torch.mean((ret["rgb0"] - target) ** 2)).backward()
+            results[guard] = ([ret[k].detach() for k in ("rgb_map", "disp_map", "acc_map", "raw", "rgb0", "disp0", "acc0", "z_std")]
+                              + [p.grad.clone() for p in list(net_c.parameters()) + list(net_f.parameters())] + [rd.grad.clone()])
+    finally:
+        ops.resident_guard(saved[0])
+        ops.mlp_arithmetic(saved[1])
+    for guard in ("fallback", "strict"):
+        for i, (a, b) in enumerate(zip(results["off"], results[guard])):
+            assert torch.equal(a, b), (guard, i)
 
 
 @pytest.mark.parametrize("rays_need_grad", [True, False], ids=["differentiable_rays", "data_rays"])
