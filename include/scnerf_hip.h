@@ -387,7 +387,7 @@ int scnerf_mlp_bwd_h3_guarded(int pt_dims, const float* d_raw, const float* pts,
                               const float* save, float* grads, float* d_pts, float* d_views, long long n_samples,
                               float* chunk_amax, int n_chunks, long long chunk_samples, int* guard_flags, int* guard_any,
                               float* guard_report, void* stream);
-/* The lean workspace of a training pass (standard network, resident arithmetic, half weight-gradient arithmetic, chunk
+/* The lean workspace of a training pass (either network variant, resident arithmetic, half weight-gradient arithmetic, chunk
  * maxima present).  feature_linear has no activation and feeds views_linears.0 linearly, so with
  *   M = sum_p dZv_p act7_p^T (128 x 256),  s = sum_p dZv_p (= d views bias),  W_vf = views_linears.0.weight[:, :256]:
  *   d views_linears.0.weight[:, :256] = M W_f^T + s b_f^T,   d feature_linear.weight = W_vf^T M,   d feature_linear.bias = W_vf^T s
@@ -395,13 +395,14 @@ int scnerf_mlp_bwd_h3_guarded(int pt_dims, const float* d_raw, const float* pts,
  * scnerf_*_h3_lean: the *_h3_guarded entry points with a flag -- lean != 0: the feature section of `save` (forward) / the
  * d feature section of `grads` (data gradients) is not written; every other output, the chunk maxima and the guard record
  * are bit-identical to lean == 0, which IS the guarded call.
- * scnerf_nerf_wgrad_h3_lean: scnerf_nerf_wgrad_h3 for such workspaces (pt_dims 3, all three tables required, arithmetic 1;
- * anything else: SCN_EINVAL).  The 256 x 256 launch takes seven jobs (layers 1 .. 7) at the unchanged chunking; the views
+ * scnerf_nerf_wgrad_h3_lean: scnerf_nerf_wgrad_h3 for such workspaces (pt_dims 3 or 4, all three tables required,
+ * arithmetic 1; anything else: SCN_EINVAL).  The 256 x 256 launch takes seven jobs (layers 1 .. 7) at the unchanged chunking; the views
  * layer's narrow launch reads act7 where it read the feature (bound: row 7 of amax_x) and reduces into scratch M and s
  * inside `workspace` (same size function); a finishing kernel on the same stream forms the three products in fp64, one
- * thread per output element, from flat_params -- the parameter buffer (reference order) of the network that ran the pass --
- * and writes or adds them and s (as d views bias) into flat_grad.  Every other gradient is bit-identical to the full group's.
- * scnerf_wgrad_lean_finish: that kernel alone (tests): M [128][256], s [128] device floats. */
+ * thread per output element, from flat_params -- the parameter buffer (reference order, scnerf_nerf_param_count(pt_dims) floats) of the network that ran
+ * the pass -- and writes or adds them and s (as d views bias) into flat_grad.  Every other gradient is bit-identical to the full group's.
+ * scnerf_wgrad_lean_finish_pd: that kernel alone (tests): M [128][256], s [128] device floats; pt_dims 3 or 4 picks the
+ * parameter offsets.  scnerf_wgrad_lean_finish: its pt_dims = 3 case. */
 int scnerf_mlp_fwd_h3_lean(int pt_dims, const float* pts, const float* viewdirs, int vd_stride, int samples_per_ray,
                            const float* wpacked, const short* stream_fwd, const float* scales, float* raw, float* save,
                            long long n_samples, float* chunk_amax, int n_chunks, long long chunk_samples, int* guard_flags,
@@ -431,6 +432,8 @@ int scnerf_nerf_wgrad_h3_lean(int pt_dims, const float* save, const float* grads
                               const float* flat_params, void* ev_before, void* ev_after, void* stream);
 int scnerf_wgrad_lean_finish(const float* M, const float* s, const float* flat_params, float* flat_grad, int accumulate,
                              void* stream);
+int scnerf_wgrad_lean_finish_pd(int pt_dims, const float* M, const float* s, const float* flat_params, float* flat_grad,
+                                int accumulate, void* stream);
 /* The exact-fp32 re-run of what the guard flagged: scnerf_mlp_fwd, scnerf_coarse_stage_fwd and scnerf_mlp_bwd (same
  * arguments, same workspaces) on the 128-sample blocks whose flag (guard_flags of the *_h3_guarded call, int
  * [ceil(n_samples / 128)]) is nonzero -- each such block bit-identical to the ungated call's, every other block untouched.

@@ -100,6 +100,7 @@ PROTOTYPES = {
                                       I, LL, P, P, P, I, P],
     "scnerf_nerf_wgrad_h3_lean": [I, P, P, P, LL, I, P, P, I, P, P, P, P, P, P, P],
     "scnerf_wgrad_lean_finish": [P, P, P, P, I, P],
+    "scnerf_wgrad_lean_finish_pd": [I, P, P, P, P, I, P],
 }
 
 

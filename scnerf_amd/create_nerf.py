@@ -45,8 +45,13 @@ class _QueryFunction(torch.autograd.Function):
             wf, planes = ops.inference_packs(net, flat)       # (forward-only: packed once per weight version)
         maxima = ops.ChunkMaxima(p.shape[0], p.device) if (train and isinstance(planes, ops.ResidentWeights)) else None
         guards = ops.guard_records(p.device, [("query", p.shape[0])], fast=planes.fast) if isinstance(planes, ops.ResidentWeights) else {}
-        raw = ops.mlp_fwd(p, v, spr, wf, save, planes=planes, maxima=maxima, guard=guards.get("query"))
+        # the lean workspace (ops.lean_workspace_scope "all"): decided ONCE here; backward follows it whatever the switches
+        # say by then.  The lean group reads three parameters: a snapshot (the flat buffer is in canonical order already)
+        lean = bool(ops.lean_workspace_scope() == "all" and maxima is not None and ops.wgrad_arithmetic() == "half")
+        raw = ops.mlp_fwd(p, v, spr, wf, save, planes=planes, maxima=maxima, guard=guards.get("query"), lean=lean)
         ctx.guard_bwd = guards.get("query_bwd")
+        ctx.lean = lean
+        ctx.flat_params = flat.detach().clone() if lean else None
         ctx.state = (p, v, spr, save, ops.pack_weights(flat, "bwd") if train else None, shape, viewdirs.shape, planes, maxima)
         return raw.view(*shape[:-1], 4)
 
@@ -57,13 +62,14 @@ class _QueryFunction(torch.autograd.Function):
         # points and directions that are data need no gradient: the resident kernel then leaves d_pts / d_views out
         input_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         grads, d_pts, d_views = ops.mlp_bwd(d_raw, p, v, spr, wbk, save, planes=planes, maxima=maxima, input_grad=input_grad,
-                                            guard=ctx.guard_bwd)
-        flat_grad = ops.nerf_wgrad(save, grads, d_raw, p.shape[0], maxima=maxima)
+                                            guard=ctx.guard_bwd, lean=ctx.lean)
+        flat_grad = ops.nerf_wgrad(save, grads, d_raw, p.shape[0], maxima=maxima, lean=ctx.lean, flat_params=ctx.flat_params)
         d_p = d_pts.view(shape) if input_grad else None
         d_v = d_views.view(-1, spr, 3).sum(1).view(vshape) if input_grad else None
         gs = [flat_grad[ML.PARAM_OFFSETS[n]: ML.PARAM_OFFSETS[n] + int(torch.Size(s).numel())].view(s)
               for n, s in ML.PARAM_SHAPES]
         ctx.state = None
+        ctx.flat_params = None
         return (d_p, d_v, None, None, *gs)
 
 

@@ -878,12 +878,9 @@ int nerf_wgrad(const float* save, const float* grads, const float* d_raw, long l
     hipLaunchKernelGGL(wgrad_reduce_multi_kernel, dim3(blocks), dim3(256), 0, st, jobs);
     rc = scn_launch_status();
     if (rc != 0 || !lean) return rc;
-    if constexpr (PD == 3) {
-        const float* M = workspace + lean_scratch_offset(n_chunks);
-        return launch_wgrad_lean_finish<3>(M, M + 128 * 256, lean_params, g, accumulate, st);
-    } else {
-        return SCN_EINVAL;           // (the lean group exists for the standard network)
-    }
+    // (both variants: the three parameters sit at Var<PD>'s offsets, the views layer is 283 columns wide in either)
+    const float* M = workspace + lean_scratch_offset(n_chunks);
+    return launch_wgrad_lean_finish<PD>(M, M + 128 * 256, lean_params, g, accumulate, st);
 }
 }  // namespace
 
@@ -921,21 +918,30 @@ extern "C" int scnerf_nerf_wgrad_h3(int pt_dims, const float* save, const float*
     return nerf_wgrad<4>(save, grads, d_raw, n_samples, n_chunks, workspace, flat_grad, accumulate, stream, amax_x, amax_z, scales, (hipEvent_t)ev_before, (hipEvent_t)ev_after);
 }
 
-// the lean group (include/scnerf_hip.h): standard network, all three tables, the half arithmetic
+// the lean group (include/scnerf_hip.h): either network variant, all three tables, the half arithmetic
 extern "C" int scnerf_nerf_wgrad_h3_lean(int pt_dims, const float* save, const float* grads, const float* d_raw,
                                          long long n_samples, int n_chunks, float* workspace, float* flat_grad,
                                          int accumulate, const float* amax_x, const float* amax_z, const float* scales,
                                          const float* flat_params, void* ev_before, void* ev_after, void* stream) {
     SCN_RETURN_IF(!save || !grads || !d_raw || !workspace || !flat_grad || n_samples < 1 || n_chunks < 1, SCN_EINVAL);
-    SCN_RETURN_IF(pt_dims != 3 || !amax_x || !amax_z || !scales || !flat_params || wgrad_arithmetic() != 1, SCN_EINVAL);
-    return nerf_wgrad<3>(save, grads, d_raw, n_samples, n_chunks, workspace, flat_grad, accumulate, stream, amax_x, amax_z, scales,
+    SCN_RETURN_IF((pt_dims != 3 && pt_dims != 4) || !amax_x || !amax_z || !scales || !flat_params || wgrad_arithmetic() != 1, SCN_EINVAL);
+    if (pt_dims == 3)
+        return nerf_wgrad<3>(save, grads, d_raw, n_samples, n_chunks, workspace, flat_grad, accumulate, stream, amax_x, amax_z, scales,
+                             (hipEvent_t)ev_before, (hipEvent_t)ev_after, flat_params);
+    return nerf_wgrad<4>(save, grads, d_raw, n_samples, n_chunks, workspace, flat_grad, accumulate, stream, amax_x, amax_z, scales,
                          (hipEvent_t)ev_before, (hipEvent_t)ev_after, flat_params);
+}
+
+extern "C" int scnerf_wgrad_lean_finish_pd(int pt_dims, const float* M, const float* s, const float* flat_params,
+                                           float* flat_grad, int accumulate, void* stream) {
+    SCN_RETURN_IF(!M || !s || !flat_params || !flat_grad || (pt_dims != 3 && pt_dims != 4), SCN_EINVAL);
+    if (pt_dims == 3) return launch_wgrad_lean_finish<3>(M, s, flat_params, flat_grad, accumulate, (hipStream_t)stream);
+    return launch_wgrad_lean_finish<4>(M, s, flat_params, flat_grad, accumulate, (hipStream_t)stream);
 }
 
 extern "C" int scnerf_wgrad_lean_finish(const float* M, const float* s, const float* flat_params, float* flat_grad,
                                         int accumulate, void* stream) {
-    SCN_RETURN_IF(!M || !s || !flat_params || !flat_grad, SCN_EINVAL);
-    return launch_wgrad_lean_finish<3>(M, s, flat_params, flat_grad, accumulate, (hipStream_t)stream);
+    return scnerf_wgrad_lean_finish_pd(3, M, s, flat_params, flat_grad, accumulate, stream);
 }
 
 // one narrow GEMM (256 x 64 / 256 x 128 with a row-major X, 128 x 256 with a tile-native X) on three fp16 products with

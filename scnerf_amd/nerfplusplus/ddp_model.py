@@ -79,9 +79,21 @@ class _NerfNetFunction(torch.autograd.Function):
         mx_b = ops.ChunkMaxima(n * sb, dev) if resident else None
         guards = ops.guard_records(dev, [("nerfpp_fg", n * sf), ("nerfpp_bg", n * sb)], fast=getattr(pl_f, "fast", False)) \
             if (isinstance(pl_f, ops.ResidentWeights) and n > 0) else {}
-        raw_f = ops.mlp_fwd(fg_pts, views, sf, wf_f, save_f, pd=3, planes=pl_f, maxima=mx_f, guard=guards.get("nerfpp_fg"))
-        raw_b = ops.mlp_fwd(bg_pts, views, sb, wf_b, save_b, pd=4, planes=pl_b, maxima=mx_b, guard=guards.get("nerfpp_bg"))
+        # the lean workspace (ops.lean_workspace_scope "all"): decided ONCE here for both networks -- the data gradients and
+        # the weight-gradient groups of this node follow it whatever the switches say by the time backward runs
+        lean = bool(ops.lean_workspace_scope() == "all" and resident and mx_f is not None and mx_b is not None
+                    and ops.wgrad_arithmetic() == "half")
+        raw_f = ops.mlp_fwd(fg_pts, views, sf, wf_f, save_f, pd=3, planes=pl_f, maxima=mx_f, guard=guards.get("nerfpp_fg"),
+                            lean=lean)
+        raw_b = ops.mlp_fwd(bg_pts, views, sb, wf_b, save_b, pd=4, planes=pl_b, maxima=mx_b, guard=guards.get("nerfpp_bg"),
+                            lean=lean)
         ctx.guards = guards
+        ctx.lean = lean
+        # (the lean group reads three parameters of each network at their canonical offsets; the module's flat buffer is
+        # in registration order: one gather is the reordering and the snapshot -- an in-place update between forward and
+        # backward does not reach the backward, as with the packed weights)
+        ctx.flat_params = (flat_f.detach().index_select(0, fg_net.canonical_to_module_index(dev)),
+                           flat_b.detach().index_select(0, bg_net.canonical_to_module_index(dev))) if lean else (None, None)
         out = {"rgb": (n, 3), "fg_weights": (n, sf), "bg_weights": (n, sb), "fg_rgb": (n, 3), "fg_depth": (n,),
                "bg_rgb": (n, 3), "bg_depth": (n,), "bg_lambda": (n,)}
         t = {k: torch.empty(sh, dtype=torch.float32, device=dev) for k, sh in out.items()}
@@ -118,18 +130,21 @@ class _NerfNetFunction(torch.autograd.Function):
                                                  _p(d_norm), n, sf, sb, _stream()), "scnerf_npp_composite_bwd")
         # both networks' data gradients first, then both weight-gradient passes (one clock recovery after the bf16
         # weight-gradient GEMMs instead of two: functional.py)
+        lean = ctx.lean
+        par_f, par_b = ctx.flat_params
         grads_f, d_pts_f, d_views_f = ops.mlp_bwd(d_raw_f, fg_pts, views, sf, wb_f, save_f, pd=3, planes=pl_f, maxima=mx_f,
-                                                  guard=ctx.guards.get("nerfpp_fg_bwd"))
+                                                  guard=ctx.guards.get("nerfpp_fg_bwd"), lean=lean)
         grads_b, d_pts_b, d_views_b = ops.mlp_bwd(d_raw_b, bg_pts, views, sb, wb_b, save_b, pd=4, planes=pl_b, maxima=mx_b,
-                                                  guard=ctx.guards.get("nerfpp_bg_bwd"))
-        flat_gf = ops.nerf_wgrad(save_f, grads_f, d_raw_f, n * sf, pd=3, maxima=mx_f)
-        flat_gb = ops.nerf_wgrad(save_b, grads_b, d_raw_b, n * sb, pd=4, maxima=mx_b)
+                                                  guard=ctx.guards.get("nerfpp_bg_bwd"), lean=lean)
+        flat_gf = ops.nerf_wgrad(save_f, grads_f, d_raw_f, n * sf, pd=3, maxima=mx_f, lean=lean, flat_params=par_f)
+        flat_gb = ops.nerf_wgrad(save_b, grads_b, d_raw_b, n * sb, pd=4, maxima=mx_b, lean=lean, flat_params=par_b)
         g_o, g_d = torch.empty_like(o), torch.empty_like(d)
         g_z = torch.empty((n, sf), dtype=torch.float32, device=dev)
         _capi.check(lib.scnerf_npp_points_bwd(_p(o), _p(d), _p(zf), _p(zb), _p(d_pts_f), _p(d_pts_b), _p(d_views_f),
                                               _p(d_views_b), _p(d_norm), _p(d_z), _p(g_o), _p(g_d), _p(g_z), n, sf, sb,
                                               _stream()), "scnerf_npp_points_bwd")
         ctx.state = None
+        ctx.flat_params = (None, None)
         n_fg = len(list(fg_net.parameters()))
         need = ctx.needs_input_grad[8:]
 

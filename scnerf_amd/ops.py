@@ -652,9 +652,9 @@ def mlp_fwd_resident(pts: Tensor, viewdirs: Tensor, samples_per_ray: int, wpacke
 
 
 def _check_lean(lean, pd, save, maxima, rw):
-    """a lean pass is a training pass of the standard network that leaves chunk maxima (lean_workspace)"""
-    if lean and (pd != 3 or save is None or maxima is None or rw.fast):
-        raise ValueError("the lean workspace needs a training pass of the standard network with chunk maxima")
+    """a lean pass is a training pass (3-D or 4-D points) that leaves chunk maxima (lean_workspace)"""
+    if lean and (pd not in (3, 4) or save is None or maxima is None or rw.fast):
+        raise ValueError("the lean workspace needs a training pass on three-product packs with chunk maxima")
 
 
 COARSE_STAGE_SAMPLES = 64        # the fused coarse stage exists for two wave tiles per ray (csrc/mlp_fwd.hip)
@@ -752,13 +752,37 @@ _FUSED_FINE_STAGE = [os.environ.get("SCNERF_FUSED_FINE_STAGE", "0") not in ("", 
 # instead of eight, a finishing kernel forms three small products in fp64.  Taken by RenderRaysFunction when the pass
 # trains on the resident arithmetic with the half weight-gradient arithmetic and chunk maxima; SCNERF_LEAN_WORKSPACE=0
 # keeps the full workspace and the twelve-GEMM group (one build can be A/B-ed).
-_LEAN_WORKSPACE = [os.environ.get("SCNERF_LEAN_WORKSPACE", "1") not in ("", "0")]
+# The switch has a scope: "off", "render" (the default: RenderRaysFunction alone) or "all" (SCNERF_LEAN_WORKSPACE=all:
+# also the NeRF++ node, both networks, and the differentiable network query node, under the same conditions).
+_LEAN_SCOPES = ("off", "render", "all")
+
+
+def _lean_scope_from_env(value: Optional[str]) -> str:
+    if value is None:
+        return "render"
+    if value in ("", "0"):
+        return "off"
+    return "all" if value == "all" else "render"
+
+
+_LEAN_WORKSPACE = [_lean_scope_from_env(os.environ.get("SCNERF_LEAN_WORKSPACE"))]
+
+
+def lean_workspace_scope(scope: Optional[str] = None) -> str:
+    """Which training nodes take the lean workspace: "off" none, "render" the render step, "all" the NeRF++ node and the
+    network query node as well.  Without an argument: the scope in force."""
+    if scope is not None:
+        if scope not in _LEAN_SCOPES:
+            raise ValueError("lean workspace scope must be one of %s" % (_LEAN_SCOPES,))
+        _LEAN_WORKSPACE[0] = scope
+    return _LEAN_WORKSPACE[0]
 
 
 def lean_workspace(on: Optional[bool] = None) -> bool:
+    """The render step's switch: True selects scope "render", False "off"; -> whether the render step runs lean."""
     if on is not None:
-        _LEAN_WORKSPACE[0] = bool(on)
-    return _LEAN_WORKSPACE[0]
+        _LEAN_WORKSPACE[0] = "render" if on else "off"
+    return _LEAN_WORKSPACE[0] != "off"
 
 
 def _no_guard():
@@ -927,8 +951,9 @@ def nerf_wgrad(save: Tensor, grads: Tensor, d_raw: Tensor, P: int, flat_grad: Op
     """All parameter gradients of one network -> flat buffer (mlp_layout.Layout parameter order);
     `accumulate`: add to `flat_grad` instead of overwriting it.
     `lean`: the workspaces come from lean passes (lean_workspace: no feature / d feature sections) -- the lean group, which
-    needs `flat_params`, the flat parameter buffer of the network that ran the pass, the chunk maxima of both resident
-    kernels and the half arithmetic; without any of them it raises (a lean workspace must never reach the full group)."""
+    needs `flat_params`, the flat parameter buffer (mlp_layout order, pd 3 or 4) of the network that ran the pass, the
+    chunk maxima of both resident kernels and the half arithmetic; without any of them it raises (a lean workspace must
+    never reach the full group)."""
     lib = _capi.load()
     chunks = wgrad_chunks(P)
     key = (chunks, str(save.device))
@@ -945,8 +970,8 @@ def nerf_wgrad(save: Tensor, grads: Tensor, d_raw: Tensor, P: int, flat_grad: Op
     if maxima is not None and maxima.scales is None:
         maxima = None
     if lean:
-        if pd != 3 or maxima is None or flat_params is None:
-            raise ValueError("the lean weight-gradient group needs the standard network, the chunk maxima of both resident "
+        if pd not in (3, 4) or maxima is None or flat_params is None:
+            raise ValueError("the lean weight-gradient group needs 3-D or 4-D points, the chunk maxima of both resident "
                              "kernels and flat_params")
         if wgrad_arithmetic() != "half":
             raise RuntimeError("the weight-gradient arithmetic was switched away from \"half\" after a lean forward pass: its "
