@@ -611,6 +611,31 @@ int scnerf_adam_step_range(float* param, const float* grad, float* exp_avg, floa
                            long long n, double lr, double beta1, double beta2, double eps,
                            double weight_decay, long long decay_lo, long long decay_hi, long long step, void* stream);
 
+/* ------------------------------------------------------------------ image metrics ---- */
+
+/* Floats of workspace scnerf_image_metrics needs for n images of c channels and h x w pixels (two fp64 partial sums per
+ * 32 x 32 tile of every channel; the pointer handed over must be 8-byte aligned).  The evaluation loops below call it
+ * once per image: NeRF/run_nerf.py:748-795, :987-1040. */
+long long scnerf_image_metrics_workspace_floats(int n, int c, int h, int w, int win);
+
+/* SSIM, mean squared error and optionally the SSIM map of x against y in one pass: what the reference's evaluation loops
+ * get from img2mse (NeRF/run_nerf_helpers.py:10, called at run_nerf.py:757-759, :995-997) and piqa.ssim.SSIM
+ * (run_nerf.py:79, :763-772, :1000-1009; nerfplusplus/ddp_test_nerf.py:122-196).  x, y: [n, c, h, w] fp32 with the ELEMENT
+ * strides given (contiguous NCHW and the .permute(2, 0, 1)[None] view of an [h, w, c] image both run without a copy).
+ * taps [win]: the normalised 1-D Gaussian, device memory; win odd, 3 .. 11.  The window is applied separably, channel by
+ * channel, without padding: the map has (h - win + 1) x (w - win + 1) entries
+ *     ss = (2 mu_x mu_y + c1) / (mu_x^2 + mu_y^2 + c1) * (2 s_xy + c2) / (s_xx + s_yy + c2).
+ * clip_x != 0 clamps x to [0, value_range] for the SSIM terms only (run_nerf.py:764-770 clips what SSIM sees, :757 scores
+ * the unclipped image).  Outputs: ssim_out [n] = mean of ss over map and channels; mse_out [n] = mean of (x - y)^2 over
+ * all c h w elements; map_out [n, c, h - win + 1, w - win + 1] or NULL.  Sums are carried in fp64 and added in a fixed
+ * order (no atomics): results are bit-identical from call to call and independent of the rest of the batch.
+ * SCN_EINVAL: a null required pointer, h < win or w < win, n < 0, c < 1, win even or outside 3 .. 11; n == 0 is a no-op. */
+int scnerf_image_metrics(const float* x, long long x_stride_n, long long x_stride_c, long long x_stride_h,
+                         long long x_stride_w, const float* y, long long y_stride_n, long long y_stride_c,
+                         long long y_stride_h, long long y_stride_w, int n, int c, int h, int w, const float* taps,
+                         int win, float c1, float c2, float value_range, int clip_x, float* ssim_out, float* mse_out,
+                         float* map_out, float* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,6 +101,8 @@ PROTOTYPES = {
     "scnerf_nerf_wgrad_h3_lean": [I, P, P, P, LL, I, P, P, I, P, P, P, P, P, P, P],
     "scnerf_wgrad_lean_finish": [P, P, P, P, I, P],
     "scnerf_wgrad_lean_finish_pd": [I, P, P, P, P, I, P],
+    # x + four element strides, y + four element strides, n c h w, taps, win, c1 c2 value_range, clip_x, outputs, workspace
+    "scnerf_image_metrics": [P, LL, LL, LL, LL, P, LL, LL, LL, LL, I, I, I, I, P, I, F, F, F, I, P, P, P, P, P],
 }
 
 
@@ -110,7 +112,8 @@ SIZE_FUNCS = {"scnerf_mlp_save_floats": [I, LL], "scnerf_mlp_grad_floats": [LL],
               "scnerf_nerf_wgrad_workspace_floats": [I],
               "scnerf_h3_scale_floats": [],
               "scnerf_wgrad_chunk_samples": [LL, I],
-              "scnerf_camera_bwd_workspace_floats": [I]}
+              "scnerf_camera_bwd_workspace_floats": [I],
+              "scnerf_image_metrics_workspace_floats": [I, I, I, I, I]}
 
 
 def bind(lib: ctypes.CDLL) -> ctypes.CDLL:

@@ -95,3 +95,25 @@ def install(share_matrix_node=True):
     from . import camera_model
     camera_model._PinholeRotNoise.share_matrix_node = bool(share_matrix_node)
     return names
+
+
+def install_metrics():
+    """Makes `from piqa.ssim import SSIM` / `from piqa.lpips import LPIPS` (NeRF/run_nerf.py:43-45, :79-80) resolve when --
+    and only when -- no real piqa can be imported: `piqa.ssim.SSIM` is scnerf_amd.metrics.SSIM (the fused HIP kernel),
+    `piqa.lpips.LPIPS` a stand-in that can be constructed and moved and returns NaN with a warning (LPIPS needs pretrained
+    weights this package does not ship; a missing metric must not look like a measured one).  An installed piqa, or
+    whatever already sits in sys.modules under that name, is never shadowed.  Returns the names registered."""
+    import importlib.util
+    import types
+    if "piqa" in sys.modules or importlib.util.find_spec("piqa") is not None:
+        return []
+    from . import metrics
+    pkg = types.ModuleType("piqa")
+    pkg.__path__ = []
+    pkg.__doc__ = "scnerf_amd's stand-in for piqa (scnerf_amd.dropin.install_metrics)"
+    pkg.ssim = types.ModuleType("piqa.ssim")
+    pkg.ssim.SSIM = metrics.SSIM
+    pkg.lpips = types.ModuleType("piqa.lpips")
+    pkg.lpips.LPIPS = metrics.LPIPSUnavailable
+    sys.modules.update({"piqa": pkg, "piqa.ssim": pkg.ssim, "piqa.lpips": pkg.lpips})
+    return ["piqa", "piqa.lpips", "piqa.ssim"]

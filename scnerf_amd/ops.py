@@ -1267,3 +1267,37 @@ def pack_rays_bwd(H, W, f2: Optional[Tensor], ndc_near: float, o: Tensor, d: Ten
                                            _p(g), _p(g_o), _p(g_d), _p(g_f), o.shape[0], _stream())
     _capi.check(st, "scnerf_pack_rays_bwd")
     return g_o, g_d, g_f
+
+
+def image_metrics(x: Tensor, y: Tensor, taps: Tensor, c1: float, c2: float, value_range: float, clip_x: bool,
+                  want_map: bool = False):
+    """SSIM [N], MSE [N] and optionally the SSIM map [N, C, H-win+1, W-win+1] of x against y, both [N, C, H, W] fp32 with
+    ANY strides (no copy is made), in one kernel pass plus a small fixed-order reduction (csrc/image_metrics.hip).  `taps`:
+    the normalised 1-D window [win] on the device."""
+    for t, name in ((x, "x"), (y, "y"), (taps, "taps")):
+        if not _capi.on_device(t):
+            raise RuntimeError("%s must live on the GPU (scnerf_amd has no CPU path)" % name)
+        if t.dtype != torch.float32:
+            raise TypeError("%s must be torch.float32, got %s" % (name, t.dtype))
+    if x.dim() != 4 or x.shape != y.shape:
+        raise ValueError("x and y must both be [N, C, H, W], got %s and %s" % (tuple(x.shape), tuple(y.shape)))
+    if taps.dim() != 1 or not taps.is_contiguous():
+        raise ValueError("taps must be a contiguous vector")
+    n, c, h, w = x.shape
+    win = taps.shape[0]
+    if win % 2 == 0 or not 3 <= win <= 11:
+        raise ValueError("the window must have an odd number of taps between 3 and 11, got %d" % win)
+    if h < win or w < win:
+        raise ValueError("images of %d x %d pixels are smaller than the %d-tap window" % (h, w, win))
+    if c < 1:
+        raise ValueError("x and y need at least one channel")
+    ssim = torch.empty(n, dtype=torch.float32, device=x.device)
+    mse = torch.empty(n, dtype=torch.float32, device=x.device)
+    ss_map = torch.empty((n, c, h - win + 1, w - win + 1), dtype=torch.float32, device=x.device) if want_map else None
+    lib = _capi.load()
+    ws = torch.empty(max(int(lib.scnerf_image_metrics_workspace_floats(n, c, h, w, win)), 2), dtype=torch.float32,
+                     device=x.device)
+    st = lib.scnerf_image_metrics(_p(x), *x.stride(), _p(y), *y.stride(), n, c, h, w, _p(taps), win, c1, c2, value_range,
+                                  int(bool(clip_x)), _p(ssim), _p(mse), _p(ss_map), _p(ws), _stream())
+    _capi.check(st, "scnerf_image_metrics")
+    return ssim, mse, ss_map
