@@ -5,7 +5,9 @@ import pytest
 import torch
 
 from oracle import nerfpp_oracle as NO
+from tests import nerfpp_reference as NR
 from tests.emu import harness as H
+from tests.nerfpp_reference import oracle_composite as _oracle_composite
 from test_nerfpp_oracle import G, GS, T
 
 pytestmark = pytest.mark.emu
@@ -140,31 +142,6 @@ def _composite_inputs(n=23, sf=70, sb=40, seed=7):
     return raw_fg, raw_bg, fg_z, z_max, bg_z, rd
 
 
-def _oracle_composite(raw_fg, raw_bg, fg_z, z_max, bg_z, rd):
-    """the compositing half of NerfNet.forward on given raw outputs (raw_bg in flipped order)"""
-    norm = torch.norm(rd, dim=-1, keepdim=True)
-    rgb, sigma = torch.sigmoid(raw_fg[..., :3]), torch.abs(raw_fg[..., 3])
-    dist = norm * torch.cat([fg_z[..., 1:] - fg_z[..., :-1], z_max[..., None] - fg_z[..., -1:]], -1)
-    alpha = 1.0 - torch.exp(-sigma * dist)
-    Tt = torch.cumprod(1.0 - alpha + NO.TINY, -1)
-    lam = Tt[..., -1]
-    Tt = torch.cat([torch.ones_like(Tt[..., :1]), Tt[..., :-1]], -1)
-    fw = alpha * Tt
-    f_rgb = (fw[..., None] * rgb).sum(-2)
-    f_depth = (fw * fg_z).sum(-1)
-    zf = torch.flip(bg_z, dims=[-1])
-    rgb_b, sig_b = torch.sigmoid(raw_bg[..., :3]), torch.abs(raw_bg[..., 3])
-    dist_b = torch.cat([zf[..., :-1] - zf[..., 1:], NO.HUGE * torch.ones_like(zf[..., :1])], -1)
-    alpha_b = 1.0 - torch.exp(-sig_b * dist_b)
-    Tb = torch.cumprod(1.0 - alpha_b + NO.TINY, -1)[..., :-1]
-    Tb = torch.cat([torch.ones_like(Tb[..., :1]), Tb], -1)
-    bw = alpha_b * Tb
-    b_rgb = lam[..., None] * (bw[..., None] * rgb_b).sum(-2)
-    b_depth = lam * (bw * zf).sum(-1)
-    return {"rgb": f_rgb + b_rgb, "fg_weights": fw, "bg_weights": bw, "fg_rgb": f_rgb, "fg_depth": f_depth,
-            "bg_rgb": b_rgb, "bg_depth": b_depth, "bg_lambda": lam}
-
-
 KEYS = ("rgb", "fg_weights", "bg_weights", "fg_rgb", "fg_depth", "bg_rgb", "bg_depth", "bg_lambda")
 
 
@@ -286,3 +263,94 @@ def test_empty_and_single_ray_edge_cases():
         np.testing.assert_allclose(out[k], ref[k].numpy(), rtol=2e-6, atol=1e-8, err_msg=k)
     # the last background sample closes the ray: its alpha is that of the HUGE interval, 1 for any sigma > 0
     assert out["bg_weights"].sum() == pytest.approx(1.0, abs=1e-5)
+
+
+# ---- any sample count, adversarial rays, against fp64 (tests/nerfpp_reference.py) ------------------------------------------
+class EmuRoute:
+    """how tests/nerfpp_reference.py's run_* functions hold buffers and call the C ABI on the interpreter"""
+    @staticmethod
+    def inp(a):
+        return None if a is None else np.ascontiguousarray(a)
+
+    @staticmethod
+    def out(shape, dtype=np.float32):
+        buf = np.full((shape[0] + 2,) + tuple(shape[1:]), NR.INT_GUARD if dtype == np.int32 else np.nan, dtype)
+        return buf, buf[1:-1]
+
+    @staticmethod
+    def call(name, *args):
+        H.call(name, *args, None)
+
+    @staticmethod
+    def host(buf):
+        return buf
+
+
+@pytest.mark.parametrize("case", NR.COMP_CASES, ids=lambda c: "sf%d_sb%d_%s" % (c[0], c[1], "all" if c[2] else "rgb"))
+def test_composite_any_sample_count_vs_fp64(case):
+    """The eight forward outputs and the five gradients of scnerf_npp_composite_fwd / _bwd on 7 rays of kinds plain / opaque /
+    tied / empty / thin tail at (sf, sb) from (2, 2) to (264, 200) -- under one pass, partial last passes, four passes -- with
+    all eight upstream gradients and with g_rgb alone, inside NaN guard rows, against the fp64 oracle within
+    K_COMPOSITE x max(the fp32 oracle's own error, 2^-23); measured figures in tests/nerfpp_reference.py."""
+    inp, _, _ = NR.composite_references(case)
+    NR.check_composite(case, NR.run_composite(EmuRoute, inp, case[2]))
+
+
+@pytest.mark.parametrize("size", NR.GEO_SIZES, ids=lambda s: "sf%d_sb%d" % s)
+def test_geometry_grazing_and_near_centre_rays_vs_fp64(size):
+    """scnerf_npp_intersect_fwd / _bwd and scnerf_npp_points_fwd / _bwd on 9 rays of closest-approach distance 1e-3 ... 0.999,
+    every tensor per ray against the fp64 oracle within K_GEOMETRY x max(fp32 oracle's error, 2^-23), inside guard rows."""
+    inp, _, _ = NR.geometry_references(size)
+    NR.check_geometry(size, NR.run_geometry(EmuRoute, inp))
+
+
+def test_points_outside_forward_without_foreground():
+    """the sf = 0, sb = 1 launch of depth2pts_outside: 18 rows of one inverse radius each, no foreground, no view directions"""
+    inp, _, _ = NR.geometry_references(NR.GEO_SIZES[0])
+    NR.check_points_outside(NR.GEO_SIZES[0], NR.run_points_outside(EmuRoute, inp))
+
+
+@pytest.mark.parametrize("case", NR.SAMPLER_CASES, ids=lambda c: "m%d_ns%d" % c)
+def test_sampler_any_bin_count(case):
+    """cdf, below, above, t and samples bit for bit against the fp32 oracle at m = 1 ... 513 bins (spike, zero, steep rows,
+    u == 0, u == 1); g_bins against the fp64 scatter-add within K_SAMPLER x max(sequential fp32 sum's error, 2^-23)."""
+    inp = NR.sampler_references(case)[0]
+    NR.check_sampler(case, NR.run_sampler(EmuRoute, inp))
+
+
+@pytest.mark.parametrize("s", NR.JITTER_S)
+def test_jitter_any_sample_count(s):
+    NR.check_jitter(s, NR.run_jitter(EmuRoute, NR.jitter_references(s)[0]))
+
+
+EINVAL, ENOSUP = -22, -95
+
+
+def test_size_limits_are_status_codes_and_leave_the_outputs_alone():
+    """Rows that no longer fit 64 KB of LDS are SCN_ENOSUP, sizes outside the ABI SCN_EINVAL -- decided on the host, before
+    any launch, with every output still as it was."""
+    f = lambda *shape: np.ones(shape, np.float32)
+    nan = lambda *shape: np.full(shape, np.nan, np.float32)
+    for m, status in ((8192, ENOSUP), (2048, ENOSUP), (32768, EINVAL)):
+        outs = [nan(1, 3), np.full((1, 3), -1, np.int32), nan(1, 3), nan(1, m + 1)]
+        assert H.lib_call_status("scnerf_npp_sample_pdf", f(1, m + 1), f(1, m), f(1, 3), *outs, 1, m, 3, None) == status, m
+        assert np.isnan(outs[0]).all() and (outs[1] == -1).all() and np.isnan(outs[2]).all() and np.isnan(outs[3]).all(), m
+    g_bins = nan(1, 16386)
+    assert H.lib_call_status("scnerf_npp_sample_pdf_bwd", f(1, 3), np.zeros((1, 3), np.int32), f(1, 3), g_bins, 1, 16385, 3,
+                             None) == ENOSUP
+    assert np.isnan(g_bins).all()
+
+    def composite(sf, sb, bwd):
+        ins = [f(1, max(sf, 1), 4), f(1, max(sb, 1), 4), f(1, max(sf, 1)), f(1), f(1, max(sb, 1)), f(1, 3)]
+        sh = NR.composite_shapes(1, max(sf, 1), max(sb, 1))
+        if bwd:
+            outs = [nan(*sh[k]) for k in NR.COMP_BWD]
+            st = H.lib_call_status("scnerf_npp_composite_bwd", *ins, f(1, 3), *[None] * 7, *outs, 1, sf, sb, None)
+        else:
+            outs = [nan(*sh[k]) for k in NR.KEYS]
+            st = H.lib_call_status("scnerf_npp_composite_fwd", *ins, *outs, 1, sf, sb, None)
+        assert all(np.isnan(o).all() for o in outs), (sf, sb, bwd)
+        return st
+    assert composite(1366, 1, True) == ENOSUP             # 3 sf + sb = 4099 floats per wave, four waves: over 64 KB
+    for bwd in (False, True):
+        assert composite(0, 4, bwd) == EINVAL and composite(4, 0, bwd) == EINVAL and composite(-1, 4, bwd) == EINVAL
