@@ -636,6 +636,47 @@ int scnerf_image_metrics(const float* x, long long x_stride_n, long long x_strid
                          int win, float c1, float c2, float value_range, int clip_x, float* ssim_out, float* mse_out,
                          float* map_out, float* workspace, void* stream);
 
+/* ------------------------------------------------------------------ training batches - */
+
+/* One training batch of n rays in ONE launch: which pixels, of which images, and their colours.  Replaces the host side
+ * of the reference's two batching branches: np.random.choice over all pixels of one image, the meshgrid and three gathers
+ * (NeRF/run_nerf.py:409-478), and the slices of a host permutation of every ray of every image, two host-to-device copies,
+ * the gather with host index arrays and np.random.shuffle at each epoch end (:368-407).
+ *
+ * Ray j of the batch is pi(position), pi a keyed bijection on [0, M): a balanced Feistel network on 2h bits, h the
+ * smallest integer >= 1 with 2^(2h) >= M, four rounds (L, R) -> (R, L ^ F(R)) on x = L 2^h + R, with
+ *     F(R) = philox4x32_10(counter = (R, 0x52420000 | mode << 8 | round, counter_lo, counter_hi), key = seed).x mod 2^h,
+ * applied again while the value is >= M (cycle walking: at most 2^(2h) - M + 1 applications, fewer than 4 expected).
+ * Every value is a pure function of the arguments: no state, no atomics, nothing read back, independent of the launch
+ * geometry.  (A uniform sample, not numpy's sample for the same seed.)
+ *
+ * mode 0, one image: M = win_w win_h, the pixels [win_x0, win_x0 + win_w) x [win_y0, win_y0 + win_h) of image
+ *   `image_pos` (the full image, or the reference's centre crop, :418-431); counter = step; position = rank n + j; the
+ *   index decodes to y = win_y0 + index / win_w, x = win_x0 + index % win_w.  The world n positions of a step are a sample
+ *   without replacement and the ranks' slices are disjoint; world n > M is an error (np.random.choice raises).
+ * mode 1, all images: M = n_sel H W (the window must be the full image); g = step world n + rank n + j, counter = the
+ *   epoch g / M, position = g % M; the index decodes to image = index / (H W), y = index % (H W) / W, x = index % W.
+ *   Every epoch visits every ray of every selected image once; a batch that straddles an epoch end continues into the
+ *   next epoch's permutation and is FULL (the reference's last batch of an epoch is short).
+ *
+ * images: [n_images, H, W, channels] contiguous, fp32 with 3 channels (image_u8 == 0) or uint8 with 3 or 4 (image_u8 != 0),
+ *   read in place; NULL when target is NULL.  A uint8 value v becomes float(double(v) / 255.0), the loaders'
+ *   (np.array(img) / 255.).astype(np.float32) bit for bit; with 4 channels the result is rgb a + (1 - a), op by op in fp32,
+ *   when white_bkgd != 0 (:167-169) and rgb alone otherwise (:171).
+ * image_ids: n_sel int64 rows of the image stack (the reference's i_train), or NULL (row = position, n_sel <= n_images).
+ *   A row outside [0, n_images) is not read: that ray's target is NaN.
+ * Outputs, each may be NULL: coords int64 [n, 2] = (x, y) (select_coords.long() / kps_list); select_inds int64 [n] =
+ *   y W + x (nerfplusplus's render_ray_from_camera); image_idx int64 [n] = the position in the selected list
+ *   (idx_in_camera_param); target fp32 [n, 3].
+ * n == 0 is a no-op.  SCN_EINVAL: a mode other than 0 / 1, sizes < 1, H W or M >= 2^40, a window outside the image or (mode 1)
+ *   not the full image, image_pos outside [0, n_sel), rank outside [0, world), world n > M in mode 0, a position past
+ *   2^63, target without images, fp32 images with channels != 3, uint8 images with channels not 3 or 4. */
+int scnerf_ray_batch(int mode, unsigned long long seed, unsigned long long step, const void* images, int image_u8,
+                     int channels, int n_images, long long H, long long W, const int64_t* image_ids, int n_sel,
+                     int image_pos, long long win_x0, long long win_y0, long long win_w, long long win_h, long long n,
+                     int rank, int world, int white_bkgd, int64_t* coords, int64_t* select_inds, int64_t* image_idx,
+                     float* target, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,6 +103,10 @@ PROTOTYPES = {
     "scnerf_wgrad_lean_finish_pd": [I, P, P, P, P, I, P],
     # x + four element strides, y + four element strides, n c h w, taps, win, c1 c2 value_range, clip_x, outputs, workspace
     "scnerf_image_metrics": [P, LL, LL, LL, LL, P, LL, LL, LL, LL, I, I, I, I, P, I, F, F, F, I, P, P, P, P, P],
+    # mode, seed, step, images, image_u8, channels, n_images H W, image_ids, n_sel, image_pos, window x0 y0 w h, n, rank,
+    # world, white_bkgd, coords, select_inds, image_idx, target
+    "scnerf_ray_batch": [I, ctypes.c_ulonglong, ctypes.c_ulonglong, P, I, I, I, LL, LL, P, I, I, LL, LL, LL, LL, LL, I, I, I,
+                         P, P, P, P, P],
 }
 
 

@@ -11,25 +11,13 @@
 #include <hip/hip_runtime.h>
 
 #include "launch.h"
+#include "philox.h"
 #include "scnerf_hip.h"
 
 namespace {
 
-struct U4 { unsigned x, y, z, w; };
-
-__host__ __device__ inline unsigned mulhi32(unsigned a, unsigned b) { return (unsigned)(((unsigned long long)a * b) >> 32); }
-
-__host__ __device__ inline U4 philox4x32_10(U4 c, unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = mulhi32(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-        const unsigned hi1 = mulhi32(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-        c = U4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
+using scn::U4;
+using scn::philox4x32_10;
 
 __device__ inline float uniform01(unsigned x) { return (float)(x >> 8) * (1.f / 16777216.f); }            // [0, 1)
 __device__ inline float uniform_open0(unsigned x) { return (float)((x >> 8) + 1u) * (1.f / 16777216.f); } // (0, 1]

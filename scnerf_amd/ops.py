@@ -1301,3 +1301,44 @@ def image_metrics(x: Tensor, y: Tensor, taps: Tensor, c1: float, c2: float, valu
                                   int(bool(clip_x)), _p(ssim), _p(mse), _p(ss_map), _p(ws), _stream())
     _capi.check(st, "scnerf_image_metrics")
     return ssim, mse, ss_map
+
+
+def ray_batch(mode: int, seed: int, step: int, images: Optional[Tensor], image_ids: Optional[Tensor], n_sel: int,
+              image_pos: int, H: int, W: int, window, n: int, rank: int = 0, world: int = 1, white_bkgd: bool = False,
+              want_coords=True, want_select_inds=True, want_image_idx=True, device=None):
+    """One training batch in ONE launch (csrc/ray_batch.hip; reference NeRF/run_nerf.py:368-478): -> (coords int64 [n, 2] as
+    (x, y), select_inds int64 [n] = y W + x, image_idx int64 [n], target fp32 [n, 3]), None where not wanted (target: where
+    `images` is None).  mode 0: n pixels of the window (x0, y0, w, h) of selected image `image_pos`, without replacement;
+    mode 1: the next n rays of a permutation of every ray of the n_sel selected images.  `images`: [n_images, H, W, 3] fp32
+    or [n_images, H, W, 3 | 4] uint8, read in place; `image_ids`: int64 [n_sel] rows of it, or None.  Nothing here makes
+    the host wait for the device."""
+    u8, channels, n_images = 0, 3, max(int(n_sel), 1)
+    if images is not None:
+        if not _capi.on_device(images):
+            raise RuntimeError("images must live on the GPU (scnerf_amd has no CPU path)")
+        if images.dtype not in (torch.float32, torch.uint8):
+            raise TypeError("images must be torch.float32 or torch.uint8, got %s" % images.dtype)
+        if images.dim() != 4 or not images.is_contiguous() or tuple(images.shape[1:3]) != (int(H), int(W)):
+            raise ValueError("images must be contiguous [n, %d, %d, C], got %s" % (H, W, tuple(images.shape)))
+        u8, channels, n_images = int(images.dtype == torch.uint8), int(images.shape[3]), int(images.shape[0])
+        device = images.device
+    if image_ids is not None:
+        _chk(image_ids, torch.int64, "image_ids")
+        if image_ids.numel() != int(n_sel):
+            raise ValueError("image_ids must have n_sel = %d entries, got %d" % (n_sel, image_ids.numel()))
+        device = image_ids.device if device is None else device
+    if device is None:
+        raise ValueError("ray_batch needs `images`, `image_ids` or `device` to know where to put the batch")
+    n = int(n)
+    empty = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=device)
+    coords = empty((n, 2), torch.int64) if want_coords else None
+    select_inds = empty((n,), torch.int64) if want_select_inds else None
+    image_idx = empty((n,), torch.int64) if want_image_idx else None
+    target = empty((n, 3), torch.float32) if images is not None else None
+    x0, y0, w, h = (int(v) for v in window)
+    st = _capi.load().scnerf_ray_batch(int(mode), int(seed) & _MASK64, int(step), _p(images), u8, channels, n_images, int(H),
+                                       int(W), _p(image_ids), int(n_sel), int(image_pos), x0, y0, w, h, n, int(rank),
+                                       int(world), int(bool(white_bkgd)), _p(coords), _p(select_inds), _p(image_idx),
+                                       _p(target), _stream())
+    _capi.check(st, "scnerf_ray_batch")
+    return coords, select_inds, image_idx, target
