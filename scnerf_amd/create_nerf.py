@@ -38,16 +38,12 @@ class _QueryFunction(torch.autograd.Function):
         save = ops.save_workspace(p.shape[0], p.device) if train else None
         # the arithmetic in force (ops.mlp_arithmetic), as in render_rays: the resident kernels' streams + the chunk maxima
         # their weight-gradient GEMMs scale by, or the fused fp32-MFMA kernels
-        if train or p.shape[0] == 0:
-            wf = ops.pack_weights(flat, "fwd")
-            planes = ops.pack_for_arithmetic(flat, train) if p.shape[0] > 0 else None
-        else:
-            wf, planes = ops.inference_packs(net, flat)       # (forward-only: packed once per weight version)
+        wf, planes = ops.network_packs(net, flat, train, p.shape[0])     # (forward-only: packed once per weight version)
         maxima = ops.ChunkMaxima(p.shape[0], p.device) if (train and isinstance(planes, ops.ResidentWeights)) else None
         guards = ops.guard_records(p.device, [("query", p.shape[0])], fast=planes.fast) if isinstance(planes, ops.ResidentWeights) else {}
         # the lean workspace (ops.lean_workspace_scope "all"): decided ONCE here; backward follows it whatever the switches
         # say by then.  The lean group reads three parameters: a snapshot (the flat buffer is in canonical order already)
-        lean = bool(ops.lean_workspace_scope() == "all" and maxima is not None and ops.wgrad_arithmetic() == "half")
+        lean = ops.lean_decision(("all",), maxima)
         raw = ops.mlp_fwd(p, v, spr, wf, save, planes=planes, maxima=maxima, guard=guards.get("query"), lean=lean)
         ctx.guard_bwd = guards.get("query_bwd")
         ctx.lean = lean
@@ -66,11 +62,9 @@ class _QueryFunction(torch.autograd.Function):
         flat_grad = ops.nerf_wgrad(save, grads, d_raw, p.shape[0], maxima=maxima, lean=ctx.lean, flat_params=ctx.flat_params)
         d_p = d_pts.view(shape) if input_grad else None
         d_v = d_views.view(-1, spr, 3).sum(1).view(vshape) if input_grad else None
-        gs = [flat_grad[ML.PARAM_OFFSETS[n]: ML.PARAM_OFFSETS[n] + int(torch.Size(s).numel())].view(s)
-              for n, s in ML.PARAM_SHAPES]
         ctx.state = None
         ctx.flat_params = None
-        return (d_p, d_v, None, None, *gs)
+        return (d_p, d_v, None, None, *ML.layout(3).split(flat_grad))
 
 
 def _fused_applies(net, embed_fn, embeddirs_fn, viewdirs_given=True) -> bool:

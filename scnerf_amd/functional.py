@@ -77,18 +77,14 @@ class RenderRaysFunction(torch.autograd.Function):
         save_c = ops.save_workspace(n * sc, dev) if train else None
         # the packed fp32 tables + what the arithmetic in force (ops.mlp_arithmetic) needs besides them: the resident
         # kernels' streams, or nothing (the fused fp32-MFMA kernels).  Training packs per call (the weights change every
-        # step); a forward-only call takes them from the network's version-keyed cache (ops.inference_packs)
-        if train or n == 0:
-            wf_c = ops.pack_weights(flat_c, "fwd")
-            pl_c = ops.pack_for_arithmetic(flat_c, train) if n > 0 else None
-        else:
-            wf_c, pl_c = ops.inference_packs(net_c, flat_c)
+        # step); a forward-only call takes them from the network's version-keyed cache (ops.network_packs)
+        wf_c, pl_c = ops.network_packs(net_c, flat_c, train, n)
         resident = isinstance(pl_c, ops.ResidentWeights)
         # (resident kernels, training: they leave the chunk maxima the fp16 weight-gradient GEMMs scale by)
         mx_c = ops.ChunkMaxima(n * sc, dev) if (train and resident) else None
         # the lean workspace (ops.lean_workspace): decided ONCE here -- the data gradients and the weight-gradient group of
         # this call follow the decision, whatever the switches say by then
-        lean = bool(ops.lean_workspace() and mx_c is not None and ops.wgrad_arithmetic() == "half")
+        lean = ops.lean_decision(("render", "all"), mx_c)
         # (the resident kernels' scale guard, ops.resident_guard: None while it is off)
         # (one record buffer per call, every pass of both stages, forward and data gradients)
         # (forward-only with ops.inference_arithmetic("fast"): the packs say so, and such passes take no record)
@@ -131,13 +127,7 @@ class RenderRaysFunction(torch.autograd.Function):
         fine_net.require_standard()
         flat_f = fine_net.flat_parameters()
         save_f = ops.save_workspace(n * tot, dev) if train else None
-        if fine_net is net_c:
-            wf_f, pl_f = wf_c, pl_c
-        elif train or n == 0:
-            wf_f = ops.pack_weights(flat_f, "fwd")
-            pl_f = ops.pack_for_arithmetic(flat_f, train) if n > 0 else None
-        else:
-            wf_f, pl_f = ops.inference_packs(fine_net, flat_f)
+        wf_f, pl_f = (wf_c, pl_c) if fine_net is net_c else ops.network_packs(fine_net, flat_f, train, n)
         mx_f = ops.ChunkMaxima(n * tot, dev) if (train and resident) else None
         gd_f = guards.get("fine")
         # (with the guard on, and on the one-product arithmetic, the three launches: the same numbers as the fused stage)
@@ -229,10 +219,7 @@ class RenderRaysFunction(torch.autograd.Function):
             fg_f = None
 
         def split(flat):
-            if flat is None:
-                return [None] * len(ML.PARAM_SHAPES)
-            return [flat[ML.PARAM_OFFSETS[name]: ML.PARAM_OFFSETS[name] + int(torch.Size(shape).numel())].view(shape)
-                    for name, shape in ML.PARAM_SHAPES]
+            return [None] * len(ML.PARAM_SHAPES) if flat is None else ML.layout(3).split(flat)
 
         grads = split(fg_c)
         if ctx.net_f is not None:

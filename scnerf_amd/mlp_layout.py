@@ -187,6 +187,12 @@ class Layout:
         self.save_floats_per_sample = sum(w for _, w in self.save_sections)
         self._cache: Dict[str, np.ndarray] = {}
 
+    def split(self, flat):
+        """flat tensor [n_params] in this layout's parameter order (the kernels' flat gradient) -> its per-parameter
+        views, in layout order"""
+        return [flat[self.param_offsets[name]: self.param_offsets[name] + int(np.prod(shape))].view(shape)
+                for name, shape in self.param_shapes]
+
     # ---- workspace sizes ----
     def save_floats(self, P: int) -> int:
         return (self.save_floats_per_sample + MASK_WORDS_PER_SAMPLE) * padded_samples(P)

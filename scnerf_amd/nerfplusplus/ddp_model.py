@@ -66,23 +66,17 @@ class _NerfNetFunction(torch.autograd.Function):
         save_f = ops.save_workspace(n * sf, dev, 3) if train else None
         save_b = ops.save_workspace(n * sb, dev, 4) if train else None
         # the arithmetic in force (ops.mlp_arithmetic): the resident kernels' streams, as in the SCNeRF step
-        if train or n == 0:
-            pl_f = ops.pack_for_arithmetic(flat_f, train, 3, remap=fg_net.pack_remap()) if n > 0 else None
-            pl_b = ops.pack_for_arithmetic(flat_b, train, 4, remap=bg_net.pack_remap()) if n > 0 else None
-            wf_f = ops.pack_weights(flat_f, "fwd", pd=3, remap=fg_net.pack_remap())
-            wf_b = ops.pack_weights(flat_b, "fwd", pd=4, remap=bg_net.pack_remap())
-        else:                                          # (forward-only: packed once per weight version)
-            wf_f, pl_f = ops.inference_packs(fg_net, flat_f, 3, remap=fg_net.pack_remap())
-            wf_b, pl_b = ops.inference_packs(bg_net, flat_b, 4, remap=bg_net.pack_remap())
-        resident = train and isinstance(pl_f, ops.ResidentWeights)
-        mx_f = ops.ChunkMaxima(n * sf, dev) if resident else None        # (for the fp16 weight-gradient GEMMs)
-        mx_b = ops.ChunkMaxima(n * sb, dev) if resident else None
-        guards = ops.guard_records(dev, [("nerfpp_fg", n * sf), ("nerfpp_bg", n * sb)], fast=getattr(pl_f, "fast", False)) \
-            if (isinstance(pl_f, ops.ResidentWeights) and n > 0) else {}
+        # (forward-only: packed once per weight version)
+        wf_f, pl_f = ops.network_packs(fg_net, flat_f, train, n, 3, remap=fg_net.pack_remap())
+        wf_b, pl_b = ops.network_packs(bg_net, flat_b, train, n, 4, remap=bg_net.pack_remap())
+        resident = isinstance(pl_f, ops.ResidentWeights)
+        mx_f = ops.ChunkMaxima(n * sf, dev) if (train and resident) else None        # (for the fp16 weight-gradient GEMMs)
+        mx_b = ops.ChunkMaxima(n * sb, dev) if (train and resident) else None
+        guards = ops.guard_records(dev, [("nerfpp_fg", n * sf), ("nerfpp_bg", n * sb)], fast=pl_f.fast) \
+            if (resident and n > 0) else {}
         # the lean workspace (ops.lean_workspace_scope "all"): decided ONCE here for both networks -- the data gradients and
         # the weight-gradient groups of this node follow it whatever the switches say by the time backward runs
-        lean = bool(ops.lean_workspace_scope() == "all" and resident and mx_f is not None and mx_b is not None
-                    and ops.wgrad_arithmetic() == "half")
+        lean = ops.lean_decision(("all",), mx_f, mx_b)
         raw_f = ops.mlp_fwd(fg_pts, views, sf, wf_f, save_f, pd=3, planes=pl_f, maxima=mx_f, guard=guards.get("nerfpp_fg"),
                             lean=lean)
         raw_b = ops.mlp_fwd(bg_pts, views, sb, wf_b, save_b, pd=4, planes=pl_b, maxima=mx_b, guard=guards.get("nerfpp_bg"),
@@ -157,10 +151,8 @@ class _NerfNetFunction(torch.autograd.Function):
                 into.index_add_(0, net.canonical_to_module_index(flat.device), flat)
                 return [None] * len(wanted)
             lay = ML.layout(pd)
-            by_canon = {name: flat[lay.param_offsets[name]: lay.param_offsets[name] + int(torch.Size(shape).numel())].view(shape)
-                        for name, shape in lay.param_shapes}
             from .nerf_network import canonical_to_module_name
-            by_module = {canonical_to_module_name(k): v for k, v in by_canon.items()}
+            by_module = {canonical_to_module_name(name): g for (name, _), g in zip(lay.param_shapes, lay.split(flat))}
             return [by_module[name] for name, _ in net.named_parameters()]
 
         return (g_o.view(o_shape), g_d.view(o_shape), d_zmax.view(zmax_shape), g_z.view(fgz_shape), None, None, None, None,

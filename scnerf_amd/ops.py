@@ -3,11 +3,10 @@ kernels enqueued on torch's current stream.  No computation happens in Python an
 is no CPU fallback: a missing library or a CPU tensor raises."""
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import numpy as np
-import os
-
 import torch
 
 from . import _capi
@@ -265,10 +264,34 @@ def pack_weights(flat_params: Tensor, kind: str = "fwd", out: Optional[Tensor] =
     return out
 
 
+class _Switch:
+    """One process-wide switch behind a public set-or-get function: `value` is preset from the environment variable
+    `env` at import -- `parse(os.environ.get(env))` where the preset is not the value itself, else `default` when unset --
+    and a preset outside `values` raises there; `switch(v)` sets it (`set_error` for a `v` outside `values`), `switch()`
+    reads it."""
+
+    def __init__(self, values, env, default=None, set_error=None, parse=None):
+        preset = os.environ.get(env)
+        self.values, self.set_error = values, set_error
+        self.value = parse(preset) if parse is not None else (default if preset is None else preset)
+        if self.value not in values:
+            raise ValueError("%s must be one of %s, not %r" % (env, "|".join(values), self.value))
+
+    def __call__(self, value=None):
+        if value is not None:
+            if value not in self.values:
+                raise ValueError(self.set_error)
+            self.value = value
+        return self.value
+
+
+def _on_off(on: Optional[bool]) -> Optional[bool]:
+    return None if on is None else bool(on)
+
+
 MLP_ARITHMETICS = ("fp32", "resident")
-_MLP_ARITHMETIC = [os.environ.get("SCNERF_MLP_ARITHMETIC", "resident")]
-if _MLP_ARITHMETIC[0] not in MLP_ARITHMETICS:
-    raise ValueError("SCNERF_MLP_ARITHMETIC must be one of %s, not %r" % ("|".join(MLP_ARITHMETICS), _MLP_ARITHMETIC[0]))
+_MLP_ARITHMETIC = _Switch(MLP_ARITHMETICS, "SCNERF_MLP_ARITHMETIC", "resident",
+                          "mlp_arithmetic is one of " + ", ".join(MLP_ARITHMETICS))
 
 
 def mlp_arithmetic(mode: Optional[str] = None) -> str:
@@ -277,17 +300,12 @@ def mlp_arithmetic(mode: Optional[str] = None) -> str:
     (csrc/mlp_h3.h): the activation workspace is only written, for the weight-gradient GEMMs; "fp32" -- the fused
     kernels on the exact-fp32 MFMA (csrc/mlp_fwd.hip, mlp_bwd.hip): the numerical yardstick.
     Without an argument: the mode in force.  Environment preset: SCNERF_MLP_ARITHMETIC."""
-    if mode is not None:
-        if mode not in MLP_ARITHMETICS:
-            raise ValueError("mlp_arithmetic is one of " + ", ".join(MLP_ARITHMETICS))
-        _MLP_ARITHMETIC[0] = mode
-    return _MLP_ARITHMETIC[0]
+    return _MLP_ARITHMETIC(mode)
 
 
 INFERENCE_ARITHMETICS = ("same", "fast")
-_INFERENCE_ARITHMETIC = [os.environ.get("SCNERF_INFER_ARITHMETIC", "same")]
-if _INFERENCE_ARITHMETIC[0] not in INFERENCE_ARITHMETICS:
-    raise ValueError("SCNERF_INFER_ARITHMETIC must be one of %s, not %r" % ("|".join(INFERENCE_ARITHMETICS), _INFERENCE_ARITHMETIC[0]))
+_INFERENCE_ARITHMETIC = _Switch(INFERENCE_ARITHMETICS, "SCNERF_INFER_ARITHMETIC", "same",
+                                "inference_arithmetic is one of " + ", ".join(INFERENCE_ARITHMETICS))
 
 
 def inference_arithmetic(mode: Optional[str] = None) -> str:
@@ -298,19 +316,14 @@ def inference_arithmetic(mode: Optional[str] = None) -> str:
     fp16 rounding of the default's instead of fp32 rounding.  A call that tracks gradients runs exactly as without the
     switch, and so does every call under mlp_arithmetic("fp32").  "fast" passes take no scale-guard record.
     Without an argument: the mode in force.  Environment preset: SCNERF_INFER_ARITHMETIC."""
-    if mode is not None:
-        if mode not in INFERENCE_ARITHMETICS:
-            raise ValueError("inference_arithmetic is one of " + ", ".join(INFERENCE_ARITHMETICS))
-        _INFERENCE_ARITHMETIC[0] = mode
-    return _INFERENCE_ARITHMETIC[0]
+    return _INFERENCE_ARITHMETIC(mode)
 
 
 RESIDENT_GUARDS = ("off", "fallback", "report", "strict")
 # Off by default: on the headline step the fallback mode costs 1.4 - 1.5 % (medians of alternating runs in both orders,
 # profiles/r07_resident_guard.txt) -- over the half per cent a default may cost.
-_RESIDENT_GUARD = [os.environ.get("SCNERF_RESIDENT_GUARD", "off")]
-if _RESIDENT_GUARD[0] not in RESIDENT_GUARDS:
-    raise ValueError("SCNERF_RESIDENT_GUARD must be one of %s, not %r" % ("|".join(RESIDENT_GUARDS), _RESIDENT_GUARD[0]))
+_RESIDENT_GUARD = _Switch(RESIDENT_GUARDS, "SCNERF_RESIDENT_GUARD", "off",
+                          "resident_guard is one of " + ", ".join(RESIDENT_GUARDS))
 
 
 def resident_guard(mode: Optional[str] = None) -> str:
@@ -322,11 +335,7 @@ def resident_guard(mode: Optional[str] = None) -> str:
     minimum margins and trip counts (resident_margins()); "strict" -- the margins, and a pass with a tripped sample raises
     ResidentRangeError instead of running again (one host read per pass: for debugging); "off" (the default) -- the
     launches without the check.  Without an argument: the mode in force.  Environment preset: SCNERF_RESIDENT_GUARD."""
-    if mode is not None:
-        if mode not in RESIDENT_GUARDS:
-            raise ValueError("resident_guard is one of " + ", ".join(RESIDENT_GUARDS))
-        _RESIDENT_GUARD[0] = mode
-    return _RESIDENT_GUARD[0]
+    return _RESIDENT_GUARD(mode)
 
 
 class ResidentRangeError(RuntimeError):
@@ -387,7 +396,7 @@ def guard_records(device, passes, fast: bool = False) -> dict:
     them, and what earlier launches of these passes left no longer shows in resident_margins()).  The
     data-gradient record shares its pass's block flags: a block the forward ran again in fp32 runs again in the data
     gradients too.  resident_margins() reads the latest launched record of every pass."""
-    mode = _RESIDENT_GUARD[0]
+    mode = _RESIDENT_GUARD.value
     if fast:
         for name, _ in passes:
             _GUARD_LAST.pop(name, None)
@@ -418,6 +427,11 @@ def resident_margins() -> dict:
     return {name: rec.margins() for name, rec in _GUARD_LAST.items()}
 
 
+def _guard_args(guard: Optional[GuardRecord]):
+    """the three guard arguments of a resident launch (csrc/resident_guard.h): the record's, or three nulls -- no check"""
+    return guard.args() if guard is not None else (None, None, None)
+
+
 def _guard_after(guard: Optional[GuardRecord], rerun):
     """after a guarded resident launch: strict -- raise on a trip; fallback / report -- rerun(flags, max_workgroups)
     enqueues the gated exact-fp32 launch"""
@@ -433,13 +447,12 @@ def _guard_after(guard: Optional[GuardRecord], rerun):
 def pack_for_arithmetic(flat_params: Tensor, train: bool, pd: int = 3, remap=None):
     """What mlp_fwd / coarse_stage_fwd / mlp_bwd take as `planes` in the arithmetic in force: the ResidentWeights
     ("resident") or None ("fp32": the fused fp32-MFMA kernels read the packed fp32 tables only)."""
-    if _MLP_ARITHMETIC[0] == "resident":
+    if _MLP_ARITHMETIC.value == "resident":
         return pack_resident(flat_params, pd, remap=remap)
     return None
 
 
-
-_PACK_CACHE = [os.environ.get("SCNERF_PACK_CACHE", "1") != "0"]
+_PACK_CACHE = _Switch((False, True), "SCNERF_PACK_CACHE", parse=lambda preset: preset != "0")
 PACK_CACHE_STATS = {"hits": 0, "packs": 0}
 
 
@@ -450,9 +463,7 @@ def weight_pack_cache(on: Optional[bool] = None) -> bool:
     and every parameter's version (in-place optimizer steps, load_state_dict and FusedAdam.step all bump them).  Writes
     that by-pass version counting (`p.data.mul_(...)`) are invisible to it -- switch the cache off around them
     (`weight_pack_cache(False)`, SCNERF_PACK_CACHE=0) or call `forget_packs(net)`.  Training never uses it."""
-    if on is not None:
-        _PACK_CACHE[0] = bool(on)
-    return _PACK_CACHE[0]
+    return _PACK_CACHE(_on_off(on))
 
 
 def forget_packs(net) -> None:
@@ -467,12 +478,12 @@ def inference_packs(net, flat_params: Tensor, pd: int = 3, remap=None):
         PACK_CACHE_STATS["packs"] += 1
         planes = pack_for_arithmetic(flat_params, False, pd, remap=remap)
         if isinstance(planes, ResidentWeights):
-            planes.fast = _INFERENCE_ARITHMETIC[0] == "fast"
+            planes.fast = _INFERENCE_ARITHMETIC.value == "fast"
         return (pack_weights(flat_params, "fwd", pd=pd, remap=remap), planes)
-    if not _PACK_CACHE[0]:
+    if not _PACK_CACHE.value:
         return build()
-    key = (flat_params.data_ptr(), flat_params._version, tuple(p._version for p in net.parameters()), _MLP_ARITHMETIC[0],
-           _INFERENCE_ARITHMETIC[0], pd, torch.cuda.current_stream(flat_params.device).cuda_stream if flat_params.is_cuda else 0)
+    key = (flat_params.data_ptr(), flat_params._version, tuple(p._version for p in net.parameters()), _MLP_ARITHMETIC.value,
+           _INFERENCE_ARITHMETIC.value, pd, torch.cuda.current_stream(flat_params.device).cuda_stream if flat_params.is_cuda else 0)
     hit = getattr(net, "_infer_packs", None)
     if hit is not None and hit[0] == key:
         PACK_CACHE_STATS["hits"] += 1
@@ -481,6 +492,18 @@ def inference_packs(net, flat_params: Tensor, pd: int = 3, remap=None):
     # (a plain attribute, not a buffer: it must not travel in state_dict() or follow .to())
     object.__setattr__(net, "_infer_packs", (key, packs))
     return packs
+
+
+def network_packs(net, flat_params: Tensor, train: bool, n: int, pd: int = 3, remap=None):
+    """-> (packed fp32 forward tables, planes) for one call of an autograd node on `n` samples: the tables and what the
+    arithmetic in force (mlp_arithmetic) needs besides them -- the resident kernels' streams, or None (the fused fp32-MFMA
+    kernels).  Training packs per call (the weights change every step); a forward-only call takes both from the
+    network's version-keyed cache (inference_packs).  An empty batch launches no network: tables and planes = None."""
+    if train or n == 0:
+        wpacked = pack_weights(flat_params, "fwd", pd=pd, remap=remap)
+        return wpacked, (pack_for_arithmetic(flat_params, train, pd, remap=remap) if n > 0 else None)
+    return inference_packs(net, flat_params, pd, remap=remap)
+
 
 _canon_cache = {}
 
@@ -566,6 +589,33 @@ def _vd(viewdirs: Tensor):
     return viewdirs.data_ptr(), int(viewdirs.stride(0)) if viewdirs.shape[0] > 1 else 3
 
 
+def _network_args(pts: Tensor, viewdirs: Tensor, packed: Tensor, kind: str, pd: int, save: Optional[Tensor]):
+    """What mlp_fwd / mlp_bwd and their resident twins check alike: the points, the view directions, the packed fp32
+    tables of the pass (`kind` "fwd": wpacked, "bwd": wpacked_bwd) and the activation workspace, which a forward may go
+    without and must find large enough.  -> (view-direction pointer, its row stride, the layout of variant `pd`, P)."""
+    name = "wpacked" if kind == "fwd" else "wpacked_bwd"
+    _f(pts, "pts"), _f(packed, name)
+    if kind == "bwd":
+        _f(save, "save")
+    vptr, vstride = _vd(viewdirs)
+    lay = ML.layout(pd)
+    P = pts.numel() // pd
+    if packed.numel() != (lay.fwd_total if kind == "fwd" else lay.bwd_total):
+        raise ValueError(name + " has the wrong size")
+    if kind == "fwd" and save is not None:
+        _f(save, "save")
+        if save.numel() < lay.save_floats(P):
+            raise ValueError("activation workspace too small")
+    return vptr, vstride, lay, P
+
+
+def _ray_outputs(n: int, s: int, device, want_weights: bool = True):
+    """-> (rgb [n,3], disp [n], acc [n], depth [n], weights [n,s] or None): the per-ray outputs of a compositing launch"""
+    rgb = torch.empty((n, 3), dtype=torch.float32, device=device)
+    disp, acc, depth = (torch.empty((n,), dtype=torch.float32, device=device) for _ in range(3))
+    return rgb, disp, acc, depth, torch.empty((n, s), dtype=torch.float32, device=device) if want_weights else None
+
+
 _MAC_PER_SAMPLE = {3: 593408, 4: 593408 + 2 * 256 * 21}       # layer 0 and the skip layer are 21 columns wider
 
 
@@ -577,20 +627,11 @@ def mlp_fwd(pts: Tensor, viewdirs: Tensor, samples_per_ray: int, wpacked: Tensor
     `guard`: a GuardRecord (guard_records) for the resident kernel's scale guard; None: no check.
     `lean` (resident training pass of the standard network): the feature section of `save` is not written
     (lean_workspace)."""
-    _f(pts, "pts"), _f(wpacked, "wpacked")
-    vptr, vstride = _vd(viewdirs)
-    lay = ML.layout(pd)
-    P = pts.numel() // pd
-    if wpacked.numel() != lay.fwd_total:
-        raise ValueError("wpacked has the wrong size")
-    if save is not None:
-        _f(save, "save")
-        if save.numel() < lay.save_floats(P):
-            raise ValueError("activation workspace too small")
     if isinstance(planes, ResidentWeights):
         if planes.pd != pd:
             raise ValueError("resident weights of another network variant")
         return mlp_fwd_resident(pts, viewdirs, samples_per_ray, wpacked, planes, save, maxima, guard, lean=lean)
+    vptr, vstride, _, P = _network_args(pts, viewdirs, wpacked, "fwd", pd, save)
     raw = torch.empty((P, 4), dtype=torch.float32, device=pts.device)
     tag = "" if pd == 3 else "/pd4"
     if planes is not None:
@@ -610,17 +651,8 @@ def mlp_fwd_resident(pts: Tensor, viewdirs: Tensor, samples_per_ray: int, wpacke
                      guard: Optional[GuardRecord] = None, lean: bool = False) -> Tensor:
     """mlp_fwd in the resident arithmetic: one launch, three fp16 products per product, activations register-resident
     (csrc/mlp_fwd_h3.hip); save (training) receives the same workspace as mlp_fwd's."""
-    _f(pts, "pts"), _f(wpacked, "wpacked")
-    vptr, vstride = _vd(viewdirs)
     pd = rw.pd
-    lay = ML.layout(pd)
-    P = pts.numel() // pd
-    if wpacked.numel() != lay.fwd_total:
-        raise ValueError("wpacked has the wrong size")
-    if save is not None:
-        _f(save, "save")
-        if save.numel() < lay.save_floats(P):
-            raise ValueError("activation workspace too small")
+    vptr, vstride, _, P = _network_args(pts, viewdirs, wpacked, "fwd", pd, save)
     raw = torch.empty((P, 4), dtype=torch.float32, device=pts.device)
     _check_lean(lean, pd, save, maxima, rw)
     if rw.fast:
@@ -634,14 +666,10 @@ def mlp_fwd_resident(pts: Tensor, viewdirs: Tensor, samples_per_ray: int, wpacke
     with PROFILE.region("mlp_fwd_h3_kernel%s/P=%d/%s" % ("" if pd == 3 else "/pd4", P, "train" if save is not None else "infer"),
                         2 * _MAC_PER_SAMPLE[pd] * P):
         mx = maxima if save is not None else None
-        args = (pd, _p(pts), vptr, vstride, int(samples_per_ray), _p(wpacked), _p(rw.fwd), _p(rw.scales), _p(raw), _p(save), P,
-                _p(mx.x) if mx else None, mx.chunks if mx else 0, mx.chunk_samples if mx else 0)
-        if lean:
-            st = _capi.load().scnerf_mlp_fwd_h3_lean(*args, *(guard.args() if guard is not None else _no_guard()), 1, _stream())
-        elif guard is None:
-            st = _capi.load().scnerf_mlp_fwd_h3(*args, _stream())
-        else:
-            st = _capi.load().scnerf_mlp_fwd_h3_guarded(*args, *guard.args(), _stream())
+        st = _capi.load().scnerf_mlp_fwd_h3_lean(
+            pd, _p(pts), vptr, vstride, int(samples_per_ray), _p(wpacked), _p(rw.fwd), _p(rw.scales), _p(raw), _p(save), P,
+            _p(mx.x) if mx else None, mx.chunks if mx else 0, mx.chunk_samples if mx else 0, *_guard_args(guard), int(lean),
+            _stream())
     _capi.check(st, "scnerf_mlp_fwd_h3")
 
     def rerun(flags, wgs):
@@ -681,11 +709,7 @@ def coarse_stage_fwd(rays: Tensor, t_vals: Tensor, t_rand: Optional[Tensor], lin
     z = torch.empty((n, s), dtype=torch.float32, device=dev)
     pts = torch.empty((n, s, 3), dtype=torch.float32, device=dev)
     raw = torch.empty((n, s, 4), dtype=torch.float32, device=dev)
-    rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    disp = torch.empty((n,), dtype=torch.float32, device=dev)
-    acc = torch.empty((n,), dtype=torch.float32, device=dev)
-    depth = torch.empty((n,), dtype=torch.float32, device=dev)
-    w = torch.empty((n, s), dtype=torch.float32, device=dev)
+    rgb, disp, acc, depth, w = _ray_outputs(n, s, dev)
     P = n * s
     if isinstance(planes, ResidentWeights):
         if planes.pd != 3:
@@ -703,17 +727,12 @@ def coarse_stage_fwd(rays: Tensor, t_vals: Tensor, t_rand: Optional[Tensor], lin
             return z, pts, raw, rgb, disp, acc, w, depth
         with PROFILE.region("mlp_fwd_h3_kernel<coarse stage>/P=%d/%s" % (P, "train" if save is not None else "infer"),
                             2 * _MAC_PER_SAMPLE[3] * P):
-            args = (_p(rays), rays.shape[1], _p(t_vals), _p(t_rand), int(bool(lindisp)), _p(wpacked), _p(planes.fwd),
-                    _p(planes.scales), _p(save), _p(noise), int(bool(white_bkgd)), _p(z), _p(pts), _p(raw), _p(rgb), _p(disp),
-                    _p(acc), _p(depth), _p(w), n, s, _p(maxima.x) if (maxima and save is not None) else None,
-                    maxima.chunks if maxima else 0, maxima.chunk_samples if maxima else 0)
-            if lean:
-                st = _capi.load().scnerf_coarse_stage_fwd_h3_lean(*args, *(guard.args() if guard is not None else _no_guard()),
-                                                                  1, _stream())
-            elif guard is None:
-                st = _capi.load().scnerf_coarse_stage_fwd_h3(*args, _stream())
-            else:
-                st = _capi.load().scnerf_coarse_stage_fwd_h3_guarded(*args, *guard.args(), _stream())
+            st = _capi.load().scnerf_coarse_stage_fwd_h3_lean(
+                _p(rays), rays.shape[1], _p(t_vals), _p(t_rand), int(bool(lindisp)), _p(wpacked), _p(planes.fwd),
+                _p(planes.scales), _p(save), _p(noise), int(bool(white_bkgd)), _p(z), _p(pts), _p(raw), _p(rgb), _p(disp),
+                _p(acc), _p(depth), _p(w), n, s, _p(maxima.x) if (maxima and save is not None) else None,
+                maxima.chunks if maxima else 0, maxima.chunk_samples if maxima else 0, *_guard_args(guard), int(lean),
+                _stream())
         _capi.check(st, "scnerf_coarse_stage_fwd_h3")
 
         def rerun(flags, wgs):
@@ -743,7 +762,11 @@ FINE_STAGE_IMPORTANCE = (64, 128, 192)       # the fused fine stage exists for 6
 # workgroup; as a kernel of its own a CU overlaps sixteen rays of it (43 us for the batch), in front of the resident
 # network -- one wave per SIMD, nothing else resident -- every microsecond of it is exposed, eight workgroups in a row per
 # CU.  Off by default for that reason; SCNERF_FUSED_FINE_STAGE=1 switches it on.
-_FUSED_FINE_STAGE = [os.environ.get("SCNERF_FUSED_FINE_STAGE", "0") not in ("", "0")]
+_FUSED_FINE_STAGE = _Switch((False, True), "SCNERF_FUSED_FINE_STAGE", parse=lambda preset: preset not in (None, "", "0"))
+
+
+def fused_fine_stage(on: Optional[bool] = None) -> bool:
+    return _FUSED_FINE_STAGE(_on_off(on))
 
 
 # The lean workspace of a training pass (csrc/wgrad.hip): feature_linear has no activation and feeds the
@@ -765,34 +788,29 @@ def _lean_scope_from_env(value: Optional[str]) -> str:
     return "all" if value == "all" else "render"
 
 
-_LEAN_WORKSPACE = [_lean_scope_from_env(os.environ.get("SCNERF_LEAN_WORKSPACE"))]
+_LEAN_WORKSPACE = _Switch(_LEAN_SCOPES, "SCNERF_LEAN_WORKSPACE", set_error="lean workspace scope must be one of %s" % (_LEAN_SCOPES,),
+                          parse=_lean_scope_from_env)
 
 
 def lean_workspace_scope(scope: Optional[str] = None) -> str:
     """Which training nodes take the lean workspace: "off" none, "render" the render step, "all" the NeRF++ node and the
     network query node as well.  Without an argument: the scope in force."""
-    if scope is not None:
-        if scope not in _LEAN_SCOPES:
-            raise ValueError("lean workspace scope must be one of %s" % (_LEAN_SCOPES,))
-        _LEAN_WORKSPACE[0] = scope
-    return _LEAN_WORKSPACE[0]
+    return _LEAN_WORKSPACE(scope)
 
 
 def lean_workspace(on: Optional[bool] = None) -> bool:
     """The render step's switch: True selects scope "render", False "off"; -> whether the render step runs lean."""
     if on is not None:
-        _LEAN_WORKSPACE[0] = "render" if on else "off"
-    return _LEAN_WORKSPACE[0] != "off"
+        _LEAN_WORKSPACE.value = "render" if on else "off"
+    return _LEAN_WORKSPACE.value != "off"
 
 
-def _no_guard():
-    return (None, None, None)
-
-
-def fused_fine_stage(on: Optional[bool] = None) -> bool:
-    if on is not None:
-        _FUSED_FINE_STAGE[0] = bool(on)
-    return _FUSED_FINE_STAGE[0]
+def lean_decision(scopes, *maxima) -> bool:
+    """Whether a training node runs its passes lean -- the one copy of the rule: the scope in force is one of `scopes`
+    (the render step: ("render", "all"); the NeRF++ node and the query node: ("all",)), every pass of the node has its
+    chunk maxima (the resident kernels train) and the weight-gradient arithmetic is "half".  A node asks ONCE, in
+    forward: its data gradients and weight-gradient groups follow the answer whatever the switches say by then."""
+    return bool(_LEAN_WORKSPACE.value in scopes and all(m is not None for m in maxima) and wgrad_arithmetic() == "half")
 
 
 def fine_stage_fwd(rays: Tensor, z_c: Tensor, w_c: Tensor, u: Tensor, wpacked: Tensor, save: Optional[Tensor],
@@ -828,24 +846,18 @@ def fine_stage_fwd(rays: Tensor, z_c: Tensor, w_c: Tensor, u: Tensor, wpacked: T
     inds = torch.empty((n, sf), dtype=torch.int64, device=dev) if want_inds else None
     cdf = torch.empty((n, sc - 1), dtype=torch.float32, device=dev) if want_cdf else None
     raw = torch.empty((n, tot, 4), dtype=torch.float32, device=dev)
-    rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    disp = torch.empty((n,), dtype=torch.float32, device=dev)
-    acc = torch.empty((n,), dtype=torch.float32, device=dev)
-    depth = torch.empty((n,), dtype=torch.float32, device=dev)
-    w = torch.empty((n, tot), dtype=torch.float32, device=dev) if want_weights else None
+    rgb, disp, acc, depth, w = _ray_outputs(n, tot, dev, want_weights)
     P = n * tot
     mx = maxima if save is not None else None
     _check_lean(lean, 3, save, maxima, planes)
     with PROFILE.region("mlp_fwd_h3_kernel<fine stage>/P=%d/%s" % (P, "train" if save is not None else "infer"),
                         2 * _MAC_PER_SAMPLE[3] * P):
-        args = (_p(rays), rays.shape[1], _p(z_c), _p(w_c), _p(u), stride, _p(wpacked), _p(planes.fwd), _p(planes.scales), _p(save),
-                _p(noise), int(bool(white_bkgd)), _p(z_f), _p(pts_f), _p(z_s), _p(z_std), _p(inds), _p(cdf), _p(raw), _p(rgb),
-                _p(disp), _p(acc), _p(depth), _p(w), n, sc, sf, _p(mx.x) if mx else None, mx.chunks if mx else 0,
-                mx.chunk_samples if mx else 0)
-        if lean:
-            st = _capi.load().scnerf_fine_stage_fwd_h3_lean(*args, *_no_guard(), 1, _stream())
-        else:
-            st = _capi.load().scnerf_fine_stage_fwd_h3(*args, _stream())
+        # (no guard record: with the guard on the fine stage runs as three launches)
+        st = _capi.load().scnerf_fine_stage_fwd_h3_lean(
+            _p(rays), rays.shape[1], _p(z_c), _p(w_c), _p(u), stride, _p(wpacked), _p(planes.fwd), _p(planes.scales), _p(save),
+            _p(noise), int(bool(white_bkgd)), _p(z_f), _p(pts_f), _p(z_s), _p(z_std), _p(inds), _p(cdf), _p(raw), _p(rgb),
+            _p(disp), _p(acc), _p(depth), _p(w), n, sc, sf, _p(mx.x) if mx else None, mx.chunks if mx else 0,
+            mx.chunk_samples if mx else 0, *_guard_args(None), int(lean), _stream())
     _capi.check(st, "scnerf_fine_stage_fwd_h3")
     return z_f, pts_f, z_s, z_std, inds, cdf, raw, rgb, disp, acc, depth, w
 
@@ -867,12 +879,8 @@ def mlp_bwd(d_raw: Tensor, pts: Tensor, viewdirs: Tensor, samples_per_ray: int, 
                                 lean=lean)
     if lean:
         raise ValueError("the lean workspace belongs to the resident arithmetic")
-    _f(d_raw, "d_raw"), _f(pts, "pts"), _f(wpacked_bwd, "wpacked_bwd"), _f(save, "save")
-    vptr, vstride = _vd(viewdirs)
-    lay = ML.layout(pd)
-    P = pts.numel() // pd
-    if wpacked_bwd.numel() != lay.bwd_total:
-        raise ValueError("wpacked_bwd has the wrong size")
+    _f(d_raw, "d_raw")
+    vptr, vstride, _, P = _network_args(pts, viewdirs, wpacked_bwd, "bwd", pd, save)
     dev = pts.device
     grads = torch.empty(ML.grad_floats(P), dtype=torch.float32, device=dev)
     d_pts = torch.empty((P, pd), dtype=torch.float32, device=dev)
@@ -891,13 +899,9 @@ def mlp_bwd_resident(d_raw: Tensor, pts: Tensor, viewdirs: Tensor, samples_per_r
                      guard: Optional[GuardRecord] = None, lean: bool = False):
     """mlp_bwd in the resident arithmetic (csrc/mlp_bwd_h3.hip): one launch -> (grads workspace, d_pts, d_views);
     input_grad=False: the instantiation without the input gradient, d_pts = d_views = None."""
-    _f(d_raw, "d_raw"), _f(pts, "pts"), _f(wpacked_bwd, "wpacked_bwd"), _f(save, "save")
-    vptr, vstride = _vd(viewdirs)
+    _f(d_raw, "d_raw")
     pd = rw.pd
-    lay = ML.layout(pd)
-    P = pts.numel() // pd
-    if wpacked_bwd.numel() != lay.bwd_total:
-        raise ValueError("wpacked_bwd has the wrong size")
+    vptr, vstride, _, P = _network_args(pts, viewdirs, wpacked_bwd, "bwd", pd, save)
     _check_lean(lean, pd, save, maxima, rw)
     dev = pts.device
     grads = torch.empty(ML.grad_floats(P), dtype=torch.float32, device=dev)
@@ -906,15 +910,10 @@ def mlp_bwd_resident(d_raw: Tensor, pts: Tensor, viewdirs: Tensor, samples_per_r
     with PROFILE.region("mlp_bwd_h3_kernel%s/P=%d" % ("" if pd == 3 else "/pd4", P), 2 * _MAC_PER_SAMPLE[pd] * P):
         if maxima is not None:
             maxima.scales = rw.scales
-        args = (pd, _p(d_raw), _p(pts), vptr, vstride, int(samples_per_ray), _p(wpacked_bwd), _p(rw.bwd), _p(rw.scales),
-                _p(save), _p(grads), _p(d_pts), _p(d_views), P, _p(maxima.z) if maxima else None,
-                maxima.chunks if maxima else 0, maxima.chunk_samples if maxima else 0)
-        if lean:
-            st = _capi.load().scnerf_mlp_bwd_h3_lean(*args, *(guard.args() if guard is not None else _no_guard()), 1, _stream())
-        elif guard is None:
-            st = _capi.load().scnerf_mlp_bwd_h3(*args, _stream())
-        else:
-            st = _capi.load().scnerf_mlp_bwd_h3_guarded(*args, *guard.args(), _stream())
+        st = _capi.load().scnerf_mlp_bwd_h3_lean(
+            pd, _p(d_raw), _p(pts), vptr, vstride, int(samples_per_ray), _p(wpacked_bwd), _p(rw.bwd), _p(rw.scales), _p(save),
+            _p(grads), _p(d_pts), _p(d_views), P, _p(maxima.z) if maxima else None, maxima.chunks if maxima else 0,
+            maxima.chunk_samples if maxima else 0, *_guard_args(guard), int(lean), _stream())
     _capi.check(st, "scnerf_mlp_bwd_h3")
 
     def rerun(flags, wgs):
@@ -1011,12 +1010,7 @@ def composite_fwd(raw: Tensor, z: Tensor, rays: Tensor, noise: Optional[Tensor],
     if noise is not None:
         _f(noise, "noise")
     n, s = z.shape
-    dev = z.device
-    rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    disp = torch.empty((n,), dtype=torch.float32, device=dev)
-    acc = torch.empty((n,), dtype=torch.float32, device=dev)
-    depth = torch.empty((n,), dtype=torch.float32, device=dev)
-    w = torch.empty((n, s), dtype=torch.float32, device=dev) if want_weights else None
+    rgb, disp, acc, depth, w = _ray_outputs(n, s, z.device, want_weights)
     st = _capi.load().scnerf_composite_fwd(_p(raw), _p(z), _p(rays), rays.shape[1], _p(noise),
                                            int(bool(white_bkgd)), _p(rgb), _p(disp), _p(acc), _p(depth),
                                            _p(w), n, s, _stream())
