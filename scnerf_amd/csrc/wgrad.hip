@@ -4,7 +4,7 @@
 // would waste a whole MFMA tile).
 //
 // What autograd derives for every nn.Linear of the reference network
-// (/root/reference NeRF/run_nerf_helpers.py:13-21, :105-128).
+// (NeRF/run_nerf_helpers.py:13-21, :105-128).
 //
 // dZ and X are the row-major [P][ld] tensors left in HBM by mlp_bwd.hip / the training forward,
 // so both MFMA operands are 128-byte row segments: lane l supplies A[i = l&31][k = l>>5] =
@@ -12,6 +12,20 @@
 // whole [BN x BK] output for a contiguous chunk of samples, staging 16 samples at a time through
 // double-buffered LDS; partial results go to a workspace and a second kernel reduces them in a
 // fixed order (deterministic; 64 MB per 256x256 layer at 256 chunks is ~25 us of HBM time).
+//
+// The file is kernels first (the generic GEMM, vecmat, rows4, the reductions, the lean group's finishing kernel; the
+// 256 x 256, tiles and fp16 kernels are in their own headers), then the host side:
+//   launchers      one per kernel family: opt into the LDS size, launch, report the status
+//   descriptors    Operand / Target / Samples: what a GEMM reads, where its sums go, how the samples are cut
+//                  (chunk_samples is the one chunk rule);  Partials hands out the [G][BN][BK] (+ [G][BN]) slabs of a
+//                  workspace and fails the call rather than cross its limit;  reduce_job fills a ReduceJob, ReduceQueue
+//                  collects up to kMaxJobs of them for the merged reduction
+//   single_gemm    one GEMM with the kernel picked at run time from the operands: scnerf_wgrad and
+//                  scnerf_wgrad_half_narrow, through which the tests reach each kernel family on its own
+//   nerf_wgrad<PD> a network pass: it names the launch every gradient takes (Var<PD>::kEW fixes the narrow shapes) and
+//                  lays its slabs out below the lean group's scratch;  the three scnerf_nerf_wgrad* exports share
+//                  one body, nerf_wgrad_entry
+#include <cstdint>
 #include <cstdlib>
 #include <type_traits>
 
@@ -488,6 +502,7 @@ int launch_wgrad_lean_finish(const float* M, const float* s, const float* params
     return scn_launch_status();
 }
 
+// ---- host side: one launcher per kernel family ---------------------------------------------------------
 template <int WN, int WK, bool FAST>
 int launch_wgrad_impl(const WgradArgs& a, int G, hipStream_t stream) {
     constexpr int BN = 2 * WN * 32, BK = 2 * WK * 32;
@@ -503,8 +518,6 @@ int launch_wgrad(const WgradArgs& a, int G, hipStream_t stream) {
     if (a.a_tiled && a.b_tiled && a.n_load == BN && a.k_load == BK) return launch_wgrad_impl<WN, WK, true>(a, G, stream);
     return launch_wgrad_impl<WN, WK, false>(a, G, stream);
 }
-
-
 
 // How the 256 x 256 GEMMs (and the narrow ones with a tile-native dZ) multiply: 1 (default) = on three fp16 products per
 // product with one power-of-two scale per operand and workgroup chunk, wherever the resident kernels left the chunk maxima
@@ -551,18 +564,86 @@ int launch_wgrad_tiles(const wgt::Args& a, int G, hipStream_t stream) {
     return scn_launch_status();
 }
 
-// the same shapes on three fp16 products (wgrad_half_narrow.h)
-template <int NA, int NB, bool B_ROWMAJOR>
+// the same shapes on three fp16 products (wgrad_half_narrow.h); jobs = 2: the pair of GEMMs the arguments name, WB2: the
+// second X operand they name
+template <int NA, int NB, bool B_ROWMAJOR, int WB2 = 0>
 int launch_wgrad_half_narrow(const wgnh::Args& a, int G, hipStream_t stream, int jobs = 1) {
-    SCN_LDS_OPT_IN((wgnh::wgrad_half_narrow_kernel<NA, NB, B_ROWMAJOR>), wgnh::kLdsBytes);
-    hipLaunchKernelGGL((wgnh::wgrad_half_narrow_kernel<NA, NB, B_ROWMAJOR>), dim3(G, jobs), dim3(wgnh::kThreads), wgnh::kLdsBytes, stream, a);
+    SCN_LDS_OPT_IN((wgnh::wgrad_half_narrow_kernel<NA, NB, B_ROWMAJOR, WB2>), wgnh::kLdsBytes);
+    hipLaunchKernelGGL((wgnh::wgrad_half_narrow_kernel<NA, NB, B_ROWMAJOR, WB2>), dim3(G, jobs), dim3(wgnh::kThreads), wgnh::kLdsBytes, stream, a);
     return scn_launch_status();
 }
 
-// two narrow GEMMs of one shape on the same X, queued by wgrad_gemm and launched together (grid (G, 2))
-struct NarrowPair {
-    wgnh::Args first;
-    int n, k_load, G;
+// ---- host side: what a GEMM reads, where its sums go, how the samples are cut, where its partials lie ------
+#define SCN_TRY(expr) do { const int rc__ = (expr); SCN_RETURN_IF(rc__ != 0, rc__); } while (0)
+
+struct Operand { const float* p; int ld, load, tiled; };                // tile-native section of width ld, or row-major [P][ld]; `load` columns staged
+struct Target { float* dW; int ldo, col0, n_out, k_out; float* db; };   // dW[n * ldo + col0 + k], n < n_out, k < k_out; db [n_out] or nullptr
+
+// THE chunk rule: samples per workgroup when `chunks` workgroups share Ppad samples -- whole LDS stages, never zero.
+// The resident kernels index their chunk maxima by the same quantity (scnerf_wgrad_chunk_samples).
+long chunk_samples(long Ppad, int chunks) {
+    const long chunk = (Ppad + chunks - 1) / chunks;
+    return chunk == 0 ? kMS : (chunk + kMS - 1) / kMS * kMS;
+}
+
+struct Samples { long P, Ppad; int G; long chunk; };       // valid / padded samples, workgroups, samples per workgroup
+Samples cut(long long n_samples, int n_chunks) {
+    const long Ppad = scn::mlp::padded_samples((long)n_samples);
+    return Samples{(long)n_samples, Ppad, n_chunks, chunk_samples(Ppad, n_chunks)};
+}
+
+// the partial sums of one GEMM: w [G][BN][BK], then (bias) b [G][BN]
+struct Tile { int G, BN, BK; bool bias; };
+struct Slab { float* w; float* b; };
+long long slab_floats(const Tile& t) { return (long long)t.G * ((long long)t.BN * t.BK + (t.bias ? t.BN : 0)); }
+Slab without_bias(Slab s) { s.b = nullptr; return s; }
+
+// hands out a workspace front to back and refuses to cross `limit`
+struct Partials {
+    float* next;
+    float* limit;
+    float* take(long long floats) {
+        if (floats > limit - next) return nullptr;
+        float* p = next;
+        next += floats;
+        return p;
+    }
+    int slab(const Tile& t, Slab* s) {
+        s->w = take(slab_floats(t));
+        SCN_RETURN_IF(!s->w, SCN_EINVAL);
+        s->b = t.bias ? s->w + (long long)t.G * t.BN * t.BK : nullptr;
+        return 0;
+    }
+};
+
+// the one place a ReduceJob is filled
+ReduceJob reduce_job(const Slab& s, const Tile& t, const Target& o, int overwrite = 0, int block0 = 0) {
+    ReduceJob j;
+    j.part_w = s.w; j.part_b = s.b; j.dW = o.dW; j.db = o.db;
+    j.G = t.G; j.BN = t.BN; j.BK = t.BK; j.n_out = o.n_out; j.k_out = o.k_out; j.ldo = o.ldo; j.col0 = o.col0;
+    j.block0 = block0;
+    j.overwrite = overwrite;
+    return j;
+}
+unsigned reduce_blocks(const ReduceJob& j) { return scn_ceil_div((long)j.n_out * j.k_out + (j.db ? j.n_out : 0), 256); }
+
+int launch_reduce(const ReduceJob& j, hipStream_t st) {
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(reduce_blocks(j)), dim3(256), 0, st, j.part_w, j.part_b, j.G, j.BN, j.BK,
+                       j.n_out, j.k_out, j.dW, j.ldo, j.col0, j.db);
+    return scn_launch_status();
+}
+
+// the reductions of a pass, finished by one launch: push() refuses a job beyond kMaxJobs and places it in the merged grid
+struct ReduceQueue {
+    ReduceJobs jobs;
+    int blocks = 0;
+    explicit ReduceQueue(int accumulate) { jobs.n = 0; jobs.accumulate = accumulate; }
+    int push(const Slab& s, const Tile& t, const Target& o, int overwrite = 0) {
+        SCN_RETURN_IF(jobs.n >= kMaxJobs, SCN_EINVAL);
+        jobs.j[jobs.n] = reduce_job(s, t, o, overwrite, blocks);
+        blocks += (int)reduce_blocks(jobs.j[jobs.n++]);
+        return 0;
+    }
 };
 
 // where a narrow GEMM finds its operands' maxima (nullptr rows: stay on the fp32 MFMA)
@@ -572,10 +653,25 @@ struct NarrowScales {
     long coarse_chunk;
 };
 
+wgnh::Args narrow_args(const float* dz, const float* x, const Slab& out, const Samples& c, const NarrowScales& ns) {
+    const wgnh::Bound none{nullptr, nullptr, nullptr};
+    return wgnh::Args{dz, x, out.w, out.b, c.P, c.Ppad, c.chunk, ns.a, ns.b, ns.n_coarse, ns.coarse_chunk,
+                      nullptr, nullptr, none, nullptr, nullptr, nullptr, none};
+}
+wgt::Args tiles_args(const float* dz, const float* x, const Slab& out, const Samples& c) {
+    return wgt::Args{dz, x, out.w, out.b, c.P, c.Ppad, c.chunk};
+}
+wg256::Args one_job256(const float* dz, const float* x, const Slab& out, const Samples& c) {
+    wg256::Args a;
+    a.n_jobs = 1; a.Ppad = c.Ppad; a.chunk = c.chunk;
+    a.job[0] = wg256::Job{dz, x, out.w, out.b};
+    return a;
+}
+
 struct Shape { int BN, BK; };
 
 bool pick_shape(int n_load, int k_load, Shape* s) {
-    // (BN, BK) of the six instantiations below
+    // (BN, BK) of the six instantiations of wgrad_kernel
     if (n_load > 256 || k_load > 256) return false;
     if (n_load > 128) { s->BN = 256; s->BK = k_load > 128 ? 256 : (k_load > 64 ? 128 : 64); return true; }
     if (n_load > 64) { s->BN = 128; s->BK = k_load > 64 ? 256 : 64; return true; }
@@ -583,121 +679,113 @@ bool pick_shape(int n_load, int k_load, Shape* s) {
     return k_load <= 128;
 }
 
+// ---- one GEMM and its reduction, the kernel picked at run time from the operands: the single-GEMM exports, through
+// which the tests reach the 256 x 256, tiles, narrow and generic kernels one at a time -------------------------------
+int single_gemm(const Operand& dz, const Operand& x, const Target& o, const Samples& c, float* workspace,
+                const NarrowScales* narrow, hipStream_t st) {
+    SCN_RETURN_IF(!dz.p || !x.p || !workspace || !o.dW || c.P < 0 || c.G < 1, SCN_EINVAL);
+    SCN_RETURN_IF(dz.ld % 4 || x.ld % 4 || dz.load % 4 || x.load % 4 || o.n_out > dz.load || o.k_out > x.load, SCN_EINVAL);
+    SCN_RETURN_IF(((uintptr_t)dz.p | (uintptr_t)x.p | (uintptr_t)workspace) & 15, SCN_EINVAL);
+    Shape s;
+    SCN_RETURN_IF(!pick_shape(dz.load, x.load, &s), SCN_ENOSUP);
+    // a tile-native operand must fill the block tile exactly (its HBM block is the LDS image)
+    SCN_RETURN_IF((dz.tiled && (dz.ld != s.BN || dz.load != dz.ld)) || (x.tiled && (x.ld != s.BK || x.load != x.ld)), SCN_EINVAL);
+    const Tile tile{c.G, s.BN, s.BK, true};
+    Partials parts{workspace, workspace + slab_floats(tile)};       // (scnerf_wgrad_workspace_floats)
+    Slab slab;
+    SCN_TRY(parts.slab(tile, &slab));
+    const Slab out = o.db ? slab : without_bias(slab);
+    const int n = dz.load, k = x.load;
+    const bool narrow_shape = dz.tiled && n == dz.ld && k == x.ld &&
+                              ((n == 256 && !x.tiled && (k == 64 || k == 128)) || (n == 128 && x.tiled && k == 256));
+    int rc;
+    if (n == 256 && k == 256 && dz.tiled && x.tiled) {
+        rc = launch_wgrad256(one_job256(dz.p, x.p, out, c), c.G, st);
+    } else if (narrow_shape && narrow && narrow->a.amax && narrow->b.amax) {
+        const wgnh::Args t = narrow_args(dz.p, x.p, out, c, *narrow);
+        // (templates are instantiated in the order of first use: this order keeps the code object's layout)
+        if (k == 64) rc = launch_wgrad_half_narrow<256, 64, true>(t, c.G, st);
+        else if (k == 128) rc = launch_wgrad_half_narrow<256, 128, true>(t, c.G, st);
+        else rc = launch_wgrad_half_narrow<128, 256, false>(t, c.G, st);
+    } else if (narrow_shape) {
+        const wgt::Args t = tiles_args(dz.p, x.p, out, c);
+        if (n == 128) rc = launch_wgrad_tiles<128, 256, false>(t, c.G, st);
+        else if (k == 64) rc = launch_wgrad_tiles<256, 64, true>(t, c.G, st);
+        else rc = launch_wgrad_tiles<256, 128, true>(t, c.G, st);
+    } else {
+        const WgradArgs a{dz.p, dz.ld, dz.load, dz.tiled, x.p, x.ld, x.load, x.tiled, c.P, c.Ppad, c.chunk, slab.w, slab.b};
+        if (s.BN == 256 && s.BK == 256) rc = launch_wgrad<4, 4>(a, c.G, st);
+        else if (s.BN == 256 && s.BK == 128) rc = launch_wgrad<4, 2>(a, c.G, st);
+        else if (s.BN == 256 && s.BK == 64) rc = launch_wgrad<4, 1>(a, c.G, st);
+        else if (s.BN == 128 && s.BK == 256) rc = launch_wgrad<2, 4>(a, c.G, st);
+        else if (s.BN == 128 && s.BK == 64) rc = launch_wgrad<2, 1>(a, c.G, st);
+        else rc = launch_wgrad<1, 2>(a, c.G, st);
+    }
+    SCN_RETURN_IF(rc != 0, rc);
+    return launch_reduce(reduce_job(slab, tile, o), st);
+}
+
 }  // namespace
 
 extern "C" long long scnerf_wgrad_workspace_floats(int n_load, int k_load, int n_chunks) {
     Shape s;
     if (!pick_shape(n_load, k_load, &s) || n_chunks < 1) return -1;
-    return (long long)n_chunks * ((long long)s.BN * s.BK + s.BN);
+    return slab_floats(Tile{n_chunks, s.BN, s.BK, true});
 }
 
-namespace {
-// GEMM into partials at `workspace`; fills `job` (the reduction that finishes it) and returns the floats used
-int wgrad_gemm(const float* dz, int lda, int n_load, int n_out, int dz_tiled, const float* x, int ldb, int k_load,
-               int k_out, int x_tiled, long long n_samples, int n_chunks, float* workspace, float* dW, int ldo,
-               int col0, float* db, hipStream_t st, ReduceJob* job, long long* used, wg256::Args* batch = nullptr,
-               const NarrowScales* narrow = nullptr, NarrowPair* pair = nullptr) {
-    SCN_RETURN_IF(!dz || !x || !workspace || !dW || n_samples < 0 || n_chunks < 1, SCN_EINVAL);
-    SCN_RETURN_IF(lda % 4 || ldb % 4 || n_load % 4 || k_load % 4 || n_out > n_load || k_out > k_load, SCN_EINVAL);
-    SCN_RETURN_IF(((uintptr_t)dz | (uintptr_t)x | (uintptr_t)workspace) & 15, SCN_EINVAL);
-    Shape s;
-    SCN_RETURN_IF(!pick_shape(n_load, k_load, &s), SCN_ENOSUP);
-    // a tile-native operand must fill the block tile exactly (its HBM block is the LDS image)
-    SCN_RETURN_IF((dz_tiled && (lda != s.BN || n_load != lda)) || (x_tiled && (ldb != s.BK || k_load != ldb)), SCN_EINVAL);
-    WgradArgs a;
-    a.A = dz; a.lda = lda; a.n_load = n_load; a.a_tiled = dz_tiled;
-    a.B = x; a.ldb = ldb; a.k_load = k_load; a.b_tiled = x_tiled;
-    a.P = (long)n_samples;
-    a.Ppad = scn::mlp::padded_samples(a.P);
-    long chunk = (a.Ppad + n_chunks - 1) / n_chunks;
-    chunk = (chunk + kMS - 1) / kMS * kMS;
-    if (chunk == 0) chunk = kMS;
-    a.chunk = chunk;
-    const int G = n_chunks;
-    a.part_w = workspace;
-    a.part_b = a.part_w + (long)G * s.BN * s.BK;
-    int rc;
-    const bool both_tiled_256 = s.BN == 256 && s.BK == 256 && dz_tiled && x_tiled && n_load == 256 && k_load == 256;
-    if (both_tiled_256) {
-        // multi-GEMM kernel: queued into `batch` when the caller launches several at once
-        wg256::Args one;
-        wg256::Args* q = batch ? batch : &one;
-        if (!batch) one.n_jobs = 0;
-        SCN_RETURN_IF(q->n_jobs >= wg256::kMaxJobs, SCN_EINVAL);
-        q->Ppad = a.Ppad;
-        q->chunk = a.chunk;
-        q->job[q->n_jobs++] = wg256::Job{dz, x, a.part_w, db ? a.part_b : nullptr};
-        rc = batch ? 0 : launch_wgrad256(one, G, st);
-    } else if (dz_tiled && n_load == lda && k_load == ldb && n_out <= n_load &&
-               ((n_load == 256 && !x_tiled && (k_load == 64 || k_load == 128)) || (n_load == 128 && x_tiled && k_load == 256))) {
-        if (narrow && narrow->a.amax && narrow->b.amax) {
-            wgnh::Args t{dz, x, a.part_w, db ? a.part_b : nullptr, a.P, a.Ppad, a.chunk, narrow->a, narrow->b,
-                         narrow->n_coarse, narrow->coarse_chunk, nullptr, nullptr, wgnh::Bound{nullptr, nullptr, nullptr},
-                         nullptr, nullptr, nullptr, wgnh::Bound{nullptr, nullptr, nullptr}};
-            if (pair && n_load == 256 && pair->n == 0) {
-                pair->first = t; pair->n = 1; pair->k_load = k_load; pair->G = G;        // launched with its partner
-                rc = 0;
-            } else if (pair && n_load == 256 && pair->n == 1 && pair->k_load == k_load && pair->G == G && pair->first.B == x) {
-                wgnh::Args both = pair->first;
-                both.A_y1 = t.A; both.part_w_y1 = t.part_w; both.part_b_y1 = t.part_b; both.a_y1 = t.a;
-                pair->n = 2;
-                rc = k_load == 64 ? launch_wgrad_half_narrow<256, 64, true>(both, G, st, 2)
-                                  : launch_wgrad_half_narrow<256, 128, true>(both, G, st, 2);
-            } else if (n_load == 128) rc = launch_wgrad_half_narrow<128, 256, false>(t, G, st);
-            else if (k_load == 64) rc = launch_wgrad_half_narrow<256, 64, true>(t, G, st);
-            else rc = launch_wgrad_half_narrow<256, 128, true>(t, G, st);
-        } else {
-            wgt::Args t{dz, x, a.part_w, db ? a.part_b : nullptr, a.P, a.Ppad, a.chunk};
-            if (n_load == 128) rc = launch_wgrad_tiles<128, 256, false>(t, G, st);
-            else if (k_load == 64) rc = launch_wgrad_tiles<256, 64, true>(t, G, st);
-            else rc = launch_wgrad_tiles<256, 128, true>(t, G, st);
-        }
-    } else if (s.BN == 256 && s.BK == 256) rc = launch_wgrad<4, 4>(a, G, st);
-    else if (s.BN == 256 && s.BK == 128) rc = launch_wgrad<4, 2>(a, G, st);
-    else if (s.BN == 256 && s.BK == 64) rc = launch_wgrad<4, 1>(a, G, st);
-    else if (s.BN == 128 && s.BK == 256) rc = launch_wgrad<2, 4>(a, G, st);
-    else if (s.BN == 128 && s.BK == 64) rc = launch_wgrad<2, 1>(a, G, st);
-    else rc = launch_wgrad<1, 2>(a, G, st);
-    SCN_RETURN_IF(rc != 0, rc);
-    job->part_w = a.part_w; job->part_b = a.part_b; job->dW = dW; job->db = db;
-    job->G = G; job->BN = s.BN; job->BK = s.BK; job->n_out = n_out; job->k_out = k_out; job->ldo = ldo; job->col0 = col0;
-    job->block0 = 0;
-    *used = (long long)G * ((long long)s.BN * s.BK + s.BN);
-    return 0;
+extern "C" long long scnerf_wgrad_chunk_samples(long long n_samples, int n_chunks) {
+    if (n_samples < 0 || n_chunks < 1) return -1;
+    return chunk_samples(scn::mlp::padded_samples(n_samples), n_chunks);
 }
-}  // namespace
 
 extern "C" int scnerf_wgrad(const float* dz, int lda, int n_load, int n_out, int dz_tiled, const float* x,
                             int ldb, int k_load, int k_out, int x_tiled, long long n_samples, int n_chunks,
                             float* workspace, float* dW, int ldo, int col0, float* db, void* stream) {
-    ReduceJob j;
-    long long used;
-    hipStream_t st = (hipStream_t)stream;
-    const int rc = wgrad_gemm(dz, lda, n_load, n_out, dz_tiled, x, ldb, k_load, k_out, x_tiled, n_samples, n_chunks,
-                              workspace, dW, ldo, col0, db, st, &j, &used);
-    SCN_RETURN_IF(rc != 0, rc);
-    const long total = (long)n_out * k_out + (db ? n_out : 0);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(scn_ceil_div(total, 256)), dim3(256), 0, st, j.part_w, j.part_b,
-                       j.G, j.BN, j.BK, n_out, k_out, dW, ldo, col0, db);
-    return scn_launch_status();
+    SCN_RETURN_IF(n_samples < 0 || n_chunks < 1, SCN_EINVAL);
+    return single_gemm(Operand{dz, lda, n_load, dz_tiled}, Operand{x, ldb, k_load, x_tiled},
+                       Target{dW, ldo, col0, n_out, k_out, db}, cut(n_samples, n_chunks), workspace, nullptr,
+                       (hipStream_t)stream);
 }
 
-namespace {
-int vecmat_impl(const float* x_tiled256, const float* vec, int vec_stride, long long n_samples, int n_chunks,
-                float* workspace, float* dv, float* dvsum, int accumulate, void* stream) {
+// one narrow GEMM (256 x 64 / 256 x 128 with a row-major X, 128 x 256 with a tile-native X) on three fp16 products with
+// the maxima given per coarse chunk of coarse_chunk samples (tests: accuracy against fp64); workspace as scnerf_wgrad
+extern "C" int scnerf_wgrad_half_narrow(const float* dz_tiled, int n_load, const float* x, int k_load, int k_out,
+                                        int x_tiled, long long n_samples, int n_chunks, float* workspace, float* dW,
+                                        float* db, const float* amax_dz, const float* amax_x, int n_coarse,
+                                        long long coarse_chunk, void* stream) {
+    SCN_RETURN_IF(!amax_dz || !amax_x || n_coarse < 1 || coarse_chunk < 32, SCN_EINVAL);
+    SCN_RETURN_IF(!((n_load == 256 && !x_tiled && (k_load == 64 || k_load == 128)) || (n_load == 128 && x_tiled && k_load == 256)), SCN_ENOSUP);
+    SCN_RETURN_IF(n_samples < 0 || n_chunks < 1, SCN_EINVAL);
+    const NarrowScales ns{wgnh::Bound{amax_dz, nullptr, nullptr}, wgnh::Bound{amax_x, nullptr, nullptr}, n_coarse, (long)coarse_chunk};
+    return single_gemm(Operand{dz_tiled, n_load, n_load, 1}, Operand{x, k_load, k_load, x_tiled},
+                       Target{dW, k_out, 0, n_load, k_out, db}, cut(n_samples, n_chunks), workspace, &ns, (hipStream_t)stream);
+}
+
+// one 256 x 256 GEMM on three fp16 products with the chunk maxima given (tests: accuracy against fp64)
+extern "C" int scnerf_wgrad256_half(const float* dz_tiled, const float* x_tiled, long long n_samples, int n_chunks,
+                                    float* workspace, float* dW, float* db, const float* amax_dz, const float* amax_x,
+                                    void* stream) {
+    SCN_RETURN_IF(!dz_tiled || !x_tiled || !workspace || !dW || !amax_dz || !amax_x || n_samples < 1 || n_chunks < 1, SCN_EINVAL);
+    hipStream_t st = (hipStream_t)stream;
+    const Samples c = cut(n_samples, n_chunks);
+    const Tile tile{n_chunks, 256, 256, true};
+    Partials parts{workspace, workspace + slab_floats(tile)};
+    Slab slab;
+    SCN_TRY(parts.slab(tile, &slab));
+    if (!db) slab = without_bias(slab);
+    SCN_TRY(launch_wgrad256_half(one_job256(dz_tiled, x_tiled, slab, c), n_chunks, amax_dz, amax_x, st));
+    return launch_reduce(reduce_job(slab, tile, Target{dW, 256, 0, 256, 256, db}), st);
+}
+
+extern "C" int scnerf_vecmat(const float* x_tiled256, const float* vec, int vec_stride, long long n_samples,
+                             int n_chunks, float* workspace, float* dv, float* dvsum, void* stream) {
     SCN_RETURN_IF(!x_tiled256 || !vec || !workspace || !dv || n_samples < 0 || n_chunks < 1 || vec_stride < 1, SCN_EINVAL);
     const long n_tiles = scn::mlp::padded_samples((long)n_samples) / 32;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(vecmat_kernel, dim3(n_chunks), dim3(kThreads), 0, st, x_tiled256, vec, vec_stride,
                        (long)n_samples, n_tiles, workspace);
-    hipLaunchKernelGGL(vecmat_reduce_kernel, dim3(2), dim3(256), 0, st, workspace, n_chunks, dv, dvsum, accumulate);
+    hipLaunchKernelGGL(vecmat_reduce_kernel, dim3(2), dim3(256), 0, st, workspace, n_chunks, dv, dvsum, 0);
     return scn_launch_status();
-}
-}  // namespace
-
-extern "C" int scnerf_vecmat(const float* x_tiled256, const float* vec, int vec_stride, long long n_samples,
-                             int n_chunks, float* workspace, float* dv, float* dvsum, void* stream) {
-    return vecmat_impl(x_tiled256, vec, vec_stride, n_samples, n_chunks, workspace, dv, dvsum, 0, stream);
 }
 
 // ---- all weight gradients of one network (D=8, W=256, skip 4, view-dependent head; 3-D or 4-D point) ----
@@ -709,17 +797,14 @@ namespace {
 // the GEMM slabs behind the vecmat partials stay 16-byte aligned (the persistent kernel stores them as float4)
 long long vecmat_ws_floats(long long n_chunks) { return (257 * n_chunks + 3) / 4 * 4; }
 
-// amax_x / amax_z (or nullptr): [8][n_chunks] chunk maxima of the X / dZ operands of the eight 256 x 256 GEMMs in the
-// order they are queued below (layers 1 .. 7, feature_linear), left by the resident kernels: with them the eight run
-// on three fp16 products (wgrad256_half.h) unless the arithmetic is switched to fp32.
-// ev_before / ev_after (or nullptr): events recorded around that one launch (bench.py's per-kernel timing) -- arguments
-// of THIS call, so that no exit path can leave them armed for a later one.
-// The eight 256 x 256 GEMMs of a pass are ONE launch of (chunks, 8) workgroups, one per CU at a time: with an eighth of
+// The 256 x 256 GEMMs of a pass are ONE launch of (chunks, 8) workgroups, one per CU at a time: with an eighth of
 // the chunks the narrow GEMMs use, 256 chunks become 32 x 8 = 256 workgroups -- one wave over the chip, every workgroup
 // eight times as many samples -- and the partial slabs (256 KB each) shrink from 0.5 GB to 67 MB written and re-read.
 int big_chunks(int n_chunks) { return (n_chunks >= 8 && n_chunks % 8 == 0) ? n_chunks / 8 : n_chunks; }
 
-// the partial slabs of every GEMM of a pass (scnerf_nerf_wgrad_workspace_floats); behind them the lean group's M and s
+// What scnerf_nerf_wgrad_workspace_floats promises for the partial slabs of a pass (the Python side caches buffers by
+// it): the vecmat partials and 9 + 2 + 1 + 1 + 1 slabs at n_chunks.  A pass needs less (its 256 x 256 slabs are cut
+// into big_chunks); its Partials take this as their limit, and the lean group's M [128][256] and s [128] lie behind it.
 long long partial_floats(long long G) {
     auto blk = [&](long long bn, long long bk) { return G * (bn * bk + bn); };
     return vecmat_ws_floats(G) + 9 * blk(256, 256) + 2 * blk(256, 128) + blk(128, 256) + blk(128, 64) + blk(64, 128);
@@ -727,170 +812,168 @@ long long partial_floats(long long G) {
 long long lean_scratch_offset(int n_chunks) { return partial_floats(n_chunks); }
 constexpr long long kLeanScratchFloats = 128 * 256 + 128;
 
+// what every pass is given: the workspaces of its forward / backward, d raw [P][4], the samples and their chunks, the
+// workspace of this group (scnerf_nerf_wgrad_workspace_floats(n_chunks)) and the flat gradient
+struct PassBuffers {
+    const float* save; const float* grads; const float* d_raw;
+    long long P; int n_chunks;
+    float* workspace; float* g; int accumulate;
+    hipStream_t st;
+};
+
+// amax_x / amax_z (or nullptr): [8][big_chunks] chunk maxima of the X / dZ operands of the 256 x 256 GEMMs in the order of
+// the big launch (layers 1 .. 7, feature_linear), left by the resident kernels: with them that launch runs on three fp16
+// products (wgrad256_half.h) unless the arithmetic is switched to fp32.  With `scales` as well (rows 8 .. 11 of amax_z:
+// dZ of the views layer, dZ of layer 0, max(1, |point|) >= the encoded point, the encoded direction's bound --
+// mlp_bwd_h3_kernel.h; the feature is bounded through its layer) so do the narrow GEMMs.
+// ev_before / ev_after (or nullptr): events recorded around the big launch (bench.py's per-kernel timing) -- arguments
+// of THIS call, so that no exit path can leave them armed for a later one.
+// lean_params (the flat parameter buffer of the network that ran the pass): the LEAN group for workspaces whose
+// feature / d feature sections were not stored -- no feature_linear job (seven in the big launch, same chunking: the
+// other gradients stay bit-identical), the views layer's narrow GEMM on act7 into scratch, wgrad_lean_finish_kernel.
+struct PassOptions {
+    const float* amax_x; const float* amax_z; const float* scales;
+    hipEvent_t ev_before, ev_after;
+    const float* lean_params;
+};
+
+// A pass lays out its slabs and reduction jobs first, in the order of the flat gradient, then launches: layer 0 with the skip
+// columns, vecmat, the views layer, rows4, the big launch (trunk layers 1 .. 7 and, not lean, feature_linear), the one
+// reduction and, lean, the finishing kernel.
 template <int PD>
-int nerf_wgrad(const float* save, const float* grads, const float* d_raw, long long P, int n_chunks,
-               float* workspace, float* g, int accumulate, void* stream, const float* amax_x = nullptr,
-               const float* amax_z = nullptr, const float* scales = nullptr, hipEvent_t ev_before = nullptr,
-               hipEvent_t ev_after = nullptr, const float* lean_params = nullptr) {
-    // lean_params (the flat parameter buffer of the network that ran the pass): the LEAN group for workspaces whose
-    // feature / d feature sections were not stored -- no feature_linear job (seven in the big launch, same chunking: the
-    // other gradients stay bit-identical), the views layer's narrow GEMM on act7 into scratch, wgrad_lean_finish_kernel
+int nerf_wgrad(const PassBuffers& io, const PassOptions& o) {
     using namespace scn::mlp;
     using V = Var<PD>;
-    const bool lean = lean_params != nullptr;
-    const long long Ppad = scn::mlp::padded_samples(P);
-    auto S = [&](int sec) { return save + (long long)sec * Ppad; };
-    auto G = [&](int sec) { return grads + (long long)sec * Ppad; };
-    auto act = [&](int l) { return S(kSaveAct + 256 * l); };
-    auto dz = [&](int l) { return G(kGradDz + 256 * l); };
     constexpr int EW = V::kEW, IN = V::kInCh, SK = V::kSkipLd;
-    int rc;
-    ReduceJobs jobs;
-    jobs.n = 0;
-    jobs.accumulate = accumulate;
-    wg256::Args big;                 // the eight 256 x 256 GEMMs go out as one launch
-    big.n_jobs = 0;
-    float* ws = workspace + vecmat_ws_floats(n_chunks);   // [0, 257 G) rounded up: the vecmat partials
-    const int nb = big_chunks(n_chunks);                  // chunks of the eight 256 x 256 GEMMs
-    hipStream_t st = (hipStream_t)stream;
-    // the narrow GEMMs on three fp16 products: rows 8 .. 10 of the dZ maxima are dZ of the views layer, dZ of layer 0
-    // and max(1, |point|) >= the encoded point (mlp_bwd_h3_kernel.h); the feature is bounded through its layer
-    const bool half_narrow = amax_x && amax_z && scales && wgrad_arithmetic() == 1;
+    const bool lean = o.lean_params != nullptr;
+    const bool half_big = o.amax_x && o.amax_z && wgrad_arithmetic() == 1;
+    const bool half_narrow = half_big && o.scales;
     SCN_RETURN_IF(lean && !half_narrow, SCN_EINVAL);     // (a lean workspace has no feature sections for the full group)
-    const long coarse_chunk = (long)scnerf_wgrad_chunk_samples(P, nb);
-    auto zrow = [&](int r) { return wgnh::Bound{amax_z + (long)r * nb, nullptr, nullptr}; };
-    const NarrowScales ns_l0{zrow(9), zrow(10), nb, coarse_chunk};
-    const NarrowScales ns_l5{zrow(4), zrow(10), nb, coarse_chunk};
-    const NarrowScales ns_views{zrow(8),
-                                wgnh::Bound{amax_x ? amax_x + 7L * nb : nullptr,
-                                            scales ? scales + scn::h3::kLayerFeat * scn::h3::kScaleStride + scn::h3::kBoundA : nullptr,
-                                            scales ? scales + scn::h3::kLayerFeat * scn::h3::kScaleStride + scn::h3::kBoundB : nullptr},
-                                nb, coarse_chunk};
-    const NarrowScales* narrow = nullptr;
-    NarrowPair pair;                 // layer 0 and the skip columns of layer 5: same shape, same X -- one launch
-    pair.n = 0;
-#define SCN_WG(...)                                                                            \
-    {                                                                                          \
-        long long used__ = 0;                                                                  \
-        rc = wgrad_gemm(__VA_ARGS__, st, &jobs.j[jobs.n], &used__, &big, narrow, &pair);       \
-        if (rc != 0) return rc;                                                                \
-        ws += used__;                                                                          \
-        ++jobs.n;                                                                              \
-    }
-    // (dz, lda, n_load, n_out, tiled,  x, ldb, k_load, k_out, tiled,  P, chunks, ws, dW, ldo, col0, db)
-    // layer 0: X = encoded points (row-major, IN valid of EW columns)
-    narrow = half_narrow ? &ns_l0 : nullptr;
-    SCN_WG(dz(0), 256, 256, 256, 1, S(kSaveEpts), EW, EW, IN, 0, P, n_chunks, ws, g + V::kW0, IN, 0, g + V::kB0)
-    narrow = nullptr;
-    for (int l = 1; l <= 7; ++l) {
-        if (l == 5) {
-            narrow = half_narrow ? &ns_l5 : nullptr;
-            SCN_WG(dz(5), 256, 256, 256, 1, S(kSaveEpts), EW, EW, IN, 0, P, n_chunks, ws, g + V::trunk_w(5), SK, 0, nullptr)
-            narrow = nullptr;
-            SCN_WG(dz(5), 256, 256, 256, 1, act(4), 256, 256, 256, 1, P, nb, ws, g + V::trunk_w(5), SK, IN, g + V::trunk_b(5))
-        } else {
-            SCN_WG(dz(l), 256, 256, 256, 1, act(l - 1), 256, 256, 256, 1, P, nb, ws, g + V::trunk_w(l), 256, 0, g + V::trunk_b(l))
-        }
-    }
-    if (pair.n == 1) {               // (a lone narrow GEMM of the pair's shape: never with this network, launched for safety)
-        rc = pair.k_load == 64 ? launch_wgrad_half_narrow<256, 64, true>(pair.first, pair.G, st)
-                               : launch_wgrad_half_narrow<256, 128, true>(pair.first, pair.G, st);
-        if (rc != 0) return rc;
-        pair.n = 0;                  // (flushed: a later GEMM of the pair's shape starts a new pair instead of re-launching this one)
-    }
-    // feature_linear; alpha_linear (one output row) = d sigma^T . act7 with d sigma = d_raw[:, 3]
-    if (!lean) {
-        SCN_WG(G(kGradDfeat), 256, 256, 256, 1, act(7), 256, 256, 256, 1, P, nb, ws, g + V::kWF, 256, 0, g + V::kBF)
-    }
-    {
-        // (its partials [G][257] are finished by the merged reduction below: the 256 sums and the bias sum as two jobs)
-        hipLaunchKernelGGL(vecmat_kernel, dim3(n_chunks), dim3(kThreads), 0, st, act(7), d_raw + 3, 4, (long)P, (long)(Ppad / 32), workspace);
-        rc = scn_launch_status();
-        if (rc != 0) return rc;
-        ReduceJob& Jw = jobs.j[jobs.n++];
-        Jw.part_w = workspace; Jw.part_b = nullptr; Jw.dW = g + V::kWA; Jw.db = nullptr;
-        Jw.G = n_chunks; Jw.BN = 1; Jw.BK = 257; Jw.n_out = 1; Jw.k_out = 256; Jw.ldo = 256; Jw.col0 = 0; Jw.block0 = 0;
-        ReduceJob& Jb = jobs.j[jobs.n++];
-        Jb.part_w = workspace + 256; Jb.part_b = nullptr; Jb.dW = g + V::kBA; Jb.db = nullptr;
-        Jb.G = n_chunks; Jb.BN = 1; Jb.BK = 257; Jb.n_out = 1; Jb.k_out = 1; Jb.ldo = 1; Jb.col0 = 0; Jb.block0 = 0;
-    }
-    // views layer: [feature | encoded direction]
+    const int nc = io.n_chunks, nb = big_chunks(nc);
+    const Samples fine = cut(io.P, nc), coarse = cut(io.P, nb);
+    auto sv = [&](int sec) { return io.save + (long long)sec * fine.Ppad; };
+    auto gr = [&](int sec) { return io.grads + (long long)sec * fine.Ppad; };
+    auto act = [&](int l) { return sv(kSaveAct + 256 * l); };
+    auto dz = [&](int l) { return gr(kGradDz + 256 * l); };
+    auto zrow = [&](int r) { return wgnh::Bound{o.amax_z + (long)r * nb, nullptr, nullptr}; };
+    float* const g = io.g;
+    float* const scratch = io.workspace + lean_scratch_offset(nc);
+    hipStream_t st = io.st;
+
+    Partials parts{io.workspace, scratch};
+    ReduceQueue red(io.accumulate);
+    auto plan = [&](const Tile& t, const Target& out, Slab* s, int overwrite = 0) -> int {
+        SCN_TRY(parts.slab(t, s));
+        return red.push(*s, t, out, overwrite);
+    };
+    wg256::Args big;                 // the 256 x 256 GEMMs go out as one launch
+    big.n_jobs = 0; big.Ppad = coarse.Ppad; big.chunk = coarse.chunk;
+    auto plan_big = [&](const float* dzl, const float* x, const Target& out) -> int {
+        SCN_RETURN_IF(big.n_jobs >= wg256::kMaxJobs, SCN_EINVAL);
+        Slab s;
+        SCN_TRY(plan(Tile{nb, 256, 256, true}, out, &s));
+        big.job[big.n_jobs++] = wg256::Job{dzl, x, s.w, s.b};
+        return 0;
+    };
+    auto trunk = [&](int l, int col0) { return Target{g + V::trunk_w(l), l == 5 ? SK : 256, col0, 256, 256, g + V::trunk_b(l)}; };
+
+    float* const vm = parts.take(vecmat_ws_floats(nc));           // [G][257]: the vecmat partials
+    SCN_RETURN_IF(!vm, SCN_EINVAL);
+    Slab s_l0, s_skip;
+    SCN_TRY(plan(Tile{nc, 256, EW, true}, Target{g + V::kW0, IN, 0, 256, IN, g + V::kB0}, &s_l0));
+    for (int l = 1; l <= 4; ++l) SCN_TRY(plan_big(dz(l), act(l - 1), trunk(l, 0)));
+    SCN_TRY(plan(Tile{nc, 256, EW, true}, Target{g + V::trunk_w(5), SK, 0, 256, IN, nullptr}, &s_skip));
+    SCN_TRY(plan_big(dz(5), act(4), trunk(5, IN)));
+    for (int l = 6; l <= 7; ++l) SCN_TRY(plan_big(dz(l), act(l - 1), trunk(l, 0)));
+    if (!lean) SCN_TRY(plan_big(gr(kGradDfeat), act(7), Target{g + V::kWF, 256, 0, 256, 256, g + V::kBF}));
+
+    // layer 0 and the skip columns of layer 5: X = encoded points (row-major, IN valid of EW columns).  Half arithmetic: ONE
+    // narrow launch, grid (G, 2), whose workgroups pair up on a CU and read X once; otherwise two wgrad_tiles launches
     if (half_narrow) {
-        // one launch for both X operands of the views layer: dZ is read (and cut) once (wgrad_half_narrow.h, WB2 = 32)
-        const int Gv = n_chunks;
-        long chunk = (Ppad + Gv - 1) / Gv;
-        chunk = (chunk + kMS - 1) / kMS * kMS;
-        float* part_w = ws;
-        float* part_b = part_w + (long)Gv * 128 * 256;
-        float* part_w2 = part_b + (long)Gv * 128;
-        // (lean: X = act7, bounded by its own maxima -- row 7 of the X table -- instead of the feature behind it)
-        wgnh::Args t{G(kGradDzv), lean ? act(7) : S(kSaveFeat), part_w, part_b, (long)P, (long)Ppad, chunk, ns_views.a,
-                     lean ? wgnh::Bound{amax_x + 7L * nb, nullptr, nullptr} : ns_views.b, nb, coarse_chunk,
-                     S(kSaveEviews), part_w2, zrow(11)};
-        SCN_LDS_OPT_IN((wgnh::wgrad_half_narrow_kernel<128, 256, false, 32>), wgnh::kLdsBytes);
-        hipLaunchKernelGGL((wgnh::wgrad_half_narrow_kernel<128, 256, false, 32>), dim3(Gv), dim3(wgnh::kThreads), wgnh::kLdsBytes, st, t);
-        rc = scn_launch_status();
-        if (rc != 0) return rc;
-        ReduceJob& J1 = jobs.j[jobs.n++];
-        J1.part_w = part_w; J1.part_b = part_b; J1.dW = g + V::kWV; J1.db = g + V::kBV;
-        J1.G = Gv; J1.BN = 128; J1.BK = 256; J1.n_out = 128; J1.k_out = 256; J1.ldo = 283; J1.col0 = 0; J1.block0 = 0;
-        ReduceJob& J2 = jobs.j[jobs.n++];
-        J2.part_w = part_w2; J2.part_b = nullptr; J2.dW = g + V::kWV; J2.db = nullptr;
-        J2.G = Gv; J2.BN = 128; J2.BK = 32; J2.n_out = 128; J2.k_out = 27; J2.ldo = 283; J2.col0 = 256; J2.block0 = 0;
-        ws += (long)Gv * (128 * 256 + 128 + 128 * 32);
-        if (lean) {                  // M and s: scratch behind everything else, finished below
-            J1.dW = workspace + lean_scratch_offset(n_chunks); J1.db = J1.dW + 128 * 256;
-            J1.ldo = 256; J1.overwrite = 1;
-        }
+        wgnh::Args both = narrow_args(dz(0), sv(kSaveEpts), s_l0, fine, NarrowScales{zrow(9), zrow(10), nb, coarse.chunk});
+        both.A_y1 = dz(5); both.part_w_y1 = s_skip.w; both.part_b_y1 = nullptr; both.a_y1 = zrow(4);
+        SCN_TRY((launch_wgrad_half_narrow<256, EW, true>(both, nc, st, 2)));
     } else {
-        SCN_WG(G(kGradDzv), 128, 128, 128, 1, S(kSaveFeat), 256, 256, 256, 1, P, n_chunks, ws, g + V::kWV, 283, 0, g + V::kBV)
-        SCN_WG(G(kGradDzv), 128, 128, 128, 1, S(kSaveEviews), 32, 32, 27, 0, P, n_chunks, ws, g + V::kWV, 283, 256, nullptr)
+        SCN_TRY((launch_wgrad_tiles<256, EW, true>(tiles_args(dz(0), sv(kSaveEpts), s_l0, fine), nc, st)));
+        SCN_TRY((launch_wgrad_tiles<256, EW, true>(tiles_args(dz(5), sv(kSaveEpts), without_bias(s_skip), fine), nc, st)));
+    }
+    // alpha_linear (one output row) = d sigma^T . act7 with d sigma = d_raw[:, 3]: the 256 sums and the bias sum as two jobs
+    hipLaunchKernelGGL(vecmat_kernel, dim3(nc), dim3(kThreads), 0, st, act(7), io.d_raw + 3, 4, fine.P, fine.Ppad / 32, vm);
+    SCN_TRY(scn_launch_status());
+    SCN_TRY(red.push(Slab{vm, nullptr}, Tile{nc, 1, 257, false}, Target{g + V::kWA, 256, 0, 1, 256, nullptr}));
+    SCN_TRY(red.push(Slab{vm + 256, nullptr}, Tile{nc, 1, 257, false}, Target{g + V::kBA, 1, 0, 1, 1, nullptr}));
+    // views layer: X = [feature | encoded direction].  Half arithmetic: one narrow launch with the direction as second X
+    // operand (WB2 = 32), dZ is read (and cut) once; otherwise wgrad_tiles<128, 256> and the generic 128 x 64 kernel
+    const Target views_dir{g + V::kWV, 283, 256, 128, 27, nullptr};
+    Slab s_feat, s_dir;
+    if (half_narrow) {
+        // (lean: X = act7, bounded by its own maxima -- row 7 of the X table -- instead of the feature behind it, and the
+        // sums M and s go to the scratch whatever `accumulate` says)
+        const float* bound = o.scales + scn::h3::kLayerFeat * scn::h3::kScaleStride;
+        const wgnh::Bound b_feat{o.amax_x + 7L * nb, bound + scn::h3::kBoundA, bound + scn::h3::kBoundB};
+        const wgnh::Bound b_act7{o.amax_x + 7L * nb, nullptr, nullptr};
+        SCN_TRY(plan(Tile{nc, 128, 256, true}, lean ? Target{scratch, 256, 0, 128, 256, scratch + 128 * 256}
+                                                    : Target{g + V::kWV, 283, 0, 128, 256, g + V::kBV}, &s_feat, lean));
+        SCN_TRY(plan(Tile{nc, 128, 32, false}, views_dir, &s_dir));
+        wgnh::Args t = narrow_args(gr(kGradDzv), lean ? act(7) : sv(kSaveFeat), s_feat, fine,
+                                   NarrowScales{zrow(8), lean ? b_act7 : b_feat, nb, coarse.chunk});
+        t.B2 = sv(kSaveEviews); t.part_w2 = s_dir.w; t.b2 = zrow(11);
+        SCN_TRY((launch_wgrad_half_narrow<128, 256, false, 32>(t, nc, st)));
+    } else {
+        SCN_TRY(plan(Tile{nc, 128, 256, true}, Target{g + V::kWV, 283, 0, 128, 256, g + V::kBV}, &s_feat));
+        SCN_TRY(plan(Tile{nc, 128, 64, true}, views_dir, &s_dir));
+        SCN_TRY((launch_wgrad_tiles<128, 256, false>(tiles_args(gr(kGradDzv), sv(kSaveFeat), s_feat, fine), nc, st)));
+        const WgradArgs a{gr(kGradDzv), 128, 128, 1, sv(kSaveEviews), 32, 32, 0, fine.P, fine.Ppad, fine.chunk, s_dir.w, s_dir.b};
+        SCN_TRY((launch_wgrad<2, 1>(a, nc, st)));
     }
     // rgb_linear: dZ = d_raw[:, 0:3] (row-major), X = hidden of the views layer
-    {
-        // (rows4_kernel: the hidden layer is read once at the HBM rate; the general kernel pads three rows to a 64-row tile)
-        const int Gr = n_chunks;
-        float* part_w = ws;
-        float* part_b = ws + (long)Gr * 4 * 128;
-        hipLaunchKernelGGL(rows4_kernel, dim3(Gr), dim3(kThreads), 0, st, S(kSaveHv), d_raw, (long)P, (long)(Ppad / 32), part_w, part_b);
-        rc = scn_launch_status();
-        if (rc != 0) return rc;
-        ReduceJob& J = jobs.j[jobs.n++];
-        J.part_w = part_w; J.part_b = part_b; J.dW = g + V::kWRGB; J.db = g + V::kBRGB;
-        J.G = Gr; J.BN = 4; J.BK = 128; J.n_out = 3; J.k_out = 128; J.ldo = 128; J.col0 = 0; J.block0 = 0;
-        ws += (long)Gr * (4 * 128 + 4);
-    }
-#undef SCN_WG
-    if (big.n_jobs > 0) {
-        if (ev_before) SCN_HIP(hipEventRecord(ev_before, st));
-        rc = (amax_x && amax_z && wgrad_arithmetic() == 1) ? launch_wgrad256_half(big, nb, amax_z, amax_x, st)
-                                                            : launch_wgrad256(big, nb, st);
-        if (rc != 0) return rc;
-        if (ev_after) SCN_HIP(hipEventRecord(ev_after, st));
-    }
-    // one launch finishes all twelve GEMMs (fixed-order sums: deterministic)
-    int blocks = 0;
-    for (int i = 0; i < jobs.n; ++i) {
-        jobs.j[i].block0 = blocks;
-        const long total = (long)jobs.j[i].n_out * jobs.j[i].k_out + (jobs.j[i].db ? jobs.j[i].n_out : 0);
-        blocks += (int)scn_ceil_div(total, 256);
-    }
-    hipLaunchKernelGGL(wgrad_reduce_multi_kernel, dim3(blocks), dim3(256), 0, st, jobs);
-    rc = scn_launch_status();
-    if (rc != 0 || !lean) return rc;
+    // (rows4_kernel: the hidden layer is read once at the HBM rate; the general kernel pads three rows to a 64-row tile)
+    Slab s_rgb;
+    SCN_TRY(plan(Tile{nc, 4, 128, true}, Target{g + V::kWRGB, 128, 0, 3, 128, g + V::kBRGB}, &s_rgb));
+    hipLaunchKernelGGL(rows4_kernel, dim3(nc), dim3(kThreads), 0, st, sv(kSaveHv), io.d_raw, fine.P, fine.Ppad / 32, s_rgb.w, s_rgb.b);
+    SCN_TRY(scn_launch_status());
+    if (o.ev_before) SCN_HIP(hipEventRecord(o.ev_before, st));
+    SCN_TRY(half_big ? launch_wgrad256_half(big, nb, o.amax_z, o.amax_x, st) : launch_wgrad256(big, nb, st));
+    if (o.ev_after) SCN_HIP(hipEventRecord(o.ev_after, st));
+    // one launch finishes every GEMM (fixed-order sums: deterministic)
+    hipLaunchKernelGGL(wgrad_reduce_multi_kernel, dim3(red.blocks), dim3(256), 0, st, red.jobs);
+    SCN_TRY(scn_launch_status());
+    if (!lean) return 0;
     // (both variants: the three parameters sit at Var<PD>'s offsets, the views layer is 283 columns wide in either)
-    const float* M = workspace + lean_scratch_offset(n_chunks);
-    return launch_wgrad_lean_finish<PD>(M, M + 128 * 256, lean_params, g, accumulate, st);
+    return launch_wgrad_lean_finish<PD>(scratch, scratch + 128 * 256, o.lean_params, g, io.accumulate, st);
+}
+
+// the one body of the three exports below
+int nerf_wgrad_entry(int pt_dims, const PassBuffers& io, const PassOptions& o) {
+    SCN_RETURN_IF(!io.save || !io.grads || !io.d_raw || !io.workspace || !io.g || io.P < 1 || io.n_chunks < 1, SCN_EINVAL);
+    SCN_RETURN_IF(pt_dims != 3 && pt_dims != 4, SCN_EINVAL);
+    return pt_dims == 3 ? nerf_wgrad<3>(io, o) : nerf_wgrad<4>(io, o);
 }
 }  // namespace
 
 extern "C" int scnerf_nerf_wgrad(int pt_dims, const float* save, const float* grads, const float* d_raw,
                                  long long n_samples, int n_chunks, float* workspace, float* flat_grad,
                                  int accumulate, void* stream) {
-    SCN_RETURN_IF(!save || !grads || !d_raw || !workspace || !flat_grad || n_samples < 1 || n_chunks < 1, SCN_EINVAL);
-    SCN_RETURN_IF(pt_dims != 3 && pt_dims != 4, SCN_EINVAL);
-    if (pt_dims == 3) return nerf_wgrad<3>(save, grads, d_raw, n_samples, n_chunks, workspace, flat_grad, accumulate, stream);
-    return nerf_wgrad<4>(save, grads, d_raw, n_samples, n_chunks, workspace, flat_grad, accumulate, stream);
+    return nerf_wgrad_entry(pt_dims, PassBuffers{save, grads, d_raw, n_samples, n_chunks, workspace, flat_grad, accumulate, (hipStream_t)stream},
+                            PassOptions{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr});
+}
+
+extern "C" int scnerf_nerf_wgrad_h3(int pt_dims, const float* save, const float* grads, const float* d_raw,
+                                    long long n_samples, int n_chunks, float* workspace, float* flat_grad,
+                                    int accumulate, const float* amax_x, const float* amax_z, const float* scales,
+                                    void* ev_before, void* ev_after, void* stream) {
+    return nerf_wgrad_entry(pt_dims, PassBuffers{save, grads, d_raw, n_samples, n_chunks, workspace, flat_grad, accumulate, (hipStream_t)stream},
+                            PassOptions{amax_x, amax_z, scales, (hipEvent_t)ev_before, (hipEvent_t)ev_after, nullptr});
+}
+
+// the lean group (include/scnerf_hip.h): either network variant, all three tables, the half arithmetic
+extern "C" int scnerf_nerf_wgrad_h3_lean(int pt_dims, const float* save, const float* grads, const float* d_raw,
+                                         long long n_samples, int n_chunks, float* workspace, float* flat_grad,
+                                         int accumulate, const float* amax_x, const float* amax_z, const float* scales,
+                                         const float* flat_params, void* ev_before, void* ev_after, void* stream) {
+    SCN_RETURN_IF(!amax_x || !amax_z || !scales || !flat_params || wgrad_arithmetic() != 1, SCN_EINVAL);
+    return nerf_wgrad_entry(pt_dims, PassBuffers{save, grads, d_raw, n_samples, n_chunks, workspace, flat_grad, accumulate, (hipStream_t)stream},
+                            PassOptions{amax_x, amax_z, scales, (hipEvent_t)ev_before, (hipEvent_t)ev_after, flat_params});
 }
 
 extern "C" int scnerf_wgrad_arithmetic(int mode) {
@@ -899,38 +982,6 @@ extern "C" int scnerf_wgrad_arithmetic(int mode) {
 }
 
 extern "C" int scnerf_wgrad256_chunks(int n_chunks) { return n_chunks < 1 ? -1 : big_chunks(n_chunks); }
-
-extern "C" long long scnerf_wgrad_chunk_samples(long long n_samples, int n_chunks) {
-    if (n_samples < 0 || n_chunks < 1) return -1;
-    const long long Ppad = scn::mlp::padded_samples(n_samples);
-    long long chunk = (Ppad + n_chunks - 1) / n_chunks;
-    chunk = (chunk + kMS - 1) / kMS * kMS;
-    return chunk == 0 ? kMS : chunk;
-}
-
-extern "C" int scnerf_nerf_wgrad_h3(int pt_dims, const float* save, const float* grads, const float* d_raw,
-                                    long long n_samples, int n_chunks, float* workspace, float* flat_grad,
-                                    int accumulate, const float* amax_x, const float* amax_z, const float* scales,
-                                    void* ev_before, void* ev_after, void* stream) {
-    SCN_RETURN_IF(!save || !grads || !d_raw || !workspace || !flat_grad || n_samples < 1 || n_chunks < 1, SCN_EINVAL);
-    SCN_RETURN_IF(pt_dims != 3 && pt_dims != 4, SCN_EINVAL);
-    if (pt_dims == 3) return nerf_wgrad<3>(save, grads, d_raw, n_samples, n_chunks, workspace, flat_grad, accumulate, stream, amax_x, amax_z, scales, (hipEvent_t)ev_before, (hipEvent_t)ev_after);
-    return nerf_wgrad<4>(save, grads, d_raw, n_samples, n_chunks, workspace, flat_grad, accumulate, stream, amax_x, amax_z, scales, (hipEvent_t)ev_before, (hipEvent_t)ev_after);
-}
-
-// the lean group (include/scnerf_hip.h): either network variant, all three tables, the half arithmetic
-extern "C" int scnerf_nerf_wgrad_h3_lean(int pt_dims, const float* save, const float* grads, const float* d_raw,
-                                         long long n_samples, int n_chunks, float* workspace, float* flat_grad,
-                                         int accumulate, const float* amax_x, const float* amax_z, const float* scales,
-                                         const float* flat_params, void* ev_before, void* ev_after, void* stream) {
-    SCN_RETURN_IF(!save || !grads || !d_raw || !workspace || !flat_grad || n_samples < 1 || n_chunks < 1, SCN_EINVAL);
-    SCN_RETURN_IF((pt_dims != 3 && pt_dims != 4) || !amax_x || !amax_z || !scales || !flat_params || wgrad_arithmetic() != 1, SCN_EINVAL);
-    if (pt_dims == 3)
-        return nerf_wgrad<3>(save, grads, d_raw, n_samples, n_chunks, workspace, flat_grad, accumulate, stream, amax_x, amax_z, scales,
-                             (hipEvent_t)ev_before, (hipEvent_t)ev_after, flat_params);
-    return nerf_wgrad<4>(save, grads, d_raw, n_samples, n_chunks, workspace, flat_grad, accumulate, stream, amax_x, amax_z, scales,
-                         (hipEvent_t)ev_before, (hipEvent_t)ev_after, flat_params);
-}
 
 extern "C" int scnerf_wgrad_lean_finish_pd(int pt_dims, const float* M, const float* s, const float* flat_params,
                                            float* flat_grad, int accumulate, void* stream) {
@@ -944,51 +995,7 @@ extern "C" int scnerf_wgrad_lean_finish(const float* M, const float* s, const fl
     return scnerf_wgrad_lean_finish_pd(3, M, s, flat_params, flat_grad, accumulate, stream);
 }
 
-// one narrow GEMM (256 x 64 / 256 x 128 with a row-major X, 128 x 256 with a tile-native X) on three fp16 products with
-// the maxima given per coarse chunk of coarse_chunk samples (tests: accuracy against fp64); workspace as scnerf_wgrad
-extern "C" int scnerf_wgrad_half_narrow(const float* dz_tiled, int n_load, const float* x, int k_load, int k_out,
-                                        int x_tiled, long long n_samples, int n_chunks, float* workspace, float* dW,
-                                        float* db, const float* amax_dz, const float* amax_x, int n_coarse,
-                                        long long coarse_chunk, void* stream) {
-    SCN_RETURN_IF(!amax_dz || !amax_x || n_coarse < 1 || coarse_chunk < 32, SCN_EINVAL);
-    SCN_RETURN_IF(!((n_load == 256 && !x_tiled && (k_load == 64 || k_load == 128)) || (n_load == 128 && x_tiled && k_load == 256)), SCN_ENOSUP);
-    ReduceJob j;
-    long long used;
-    hipStream_t st = (hipStream_t)stream;
-    const NarrowScales ns{wgnh::Bound{amax_dz, nullptr, nullptr}, wgnh::Bound{amax_x, nullptr, nullptr}, n_coarse, (long)coarse_chunk};
-    const int rc = wgrad_gemm(dz_tiled, n_load, n_load, n_load, 1, x, k_load, k_load, k_out, x_tiled, n_samples, n_chunks,
-                              workspace, dW, k_out, 0, db, st, &j, &used, nullptr, &ns);
-    SCN_RETURN_IF(rc != 0, rc);
-    const long total = (long)n_load * k_out + (db ? n_load : 0);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(scn_ceil_div(total, 256)), dim3(256), 0, st, j.part_w, j.part_b,
-                       j.G, j.BN, j.BK, n_load, k_out, dW, k_out, 0, db);
-    return scn_launch_status();
-}
-
-// one 256 x 256 GEMM on three fp16 products with the chunk maxima given (tests: accuracy against fp64)
-extern "C" int scnerf_wgrad256_half(const float* dz_tiled, const float* x_tiled, long long n_samples, int n_chunks,
-                                    float* workspace, float* dW, float* db, const float* amax_dz, const float* amax_x,
-                                    void* stream) {
-    SCN_RETURN_IF(!dz_tiled || !x_tiled || !workspace || !dW || !amax_dz || !amax_x || n_samples < 1 || n_chunks < 1, SCN_EINVAL);
-    hipStream_t st = (hipStream_t)stream;
-    wg256::Args one;
-    one.n_jobs = 1;
-    one.Ppad = scn::mlp::padded_samples(n_samples);
-    one.chunk = scnerf_wgrad_chunk_samples(n_samples, n_chunks);
-    float* part_w = workspace;
-    float* part_b = workspace + (long)n_chunks * 256 * 256;
-    one.job[0] = wg256::Job{dz_tiled, x_tiled, part_w, db ? part_b : nullptr};
-    int rc = launch_wgrad256_half(one, n_chunks, amax_dz, amax_x, st);
-    SCN_RETURN_IF(rc != 0, rc);
-    const long total = 256L * 256 + (db ? 256 : 0);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(scn_ceil_div(total, 256)), dim3(256), 0, st, part_w, db ? part_b : nullptr,
-                       n_chunks, 256, 256, 256, 256, dW, 256, 0, db);
-    return scn_launch_status();
-}
-
-long long scnerf_nerf_wgrad_workspace_floats(int n_chunks) {
-    // every GEMM keeps its partials until the single reduction launch: 9 x (256 x 256), 2 x (256 x 128 | 64),
-    // (128 x 256), (128 x 64), (64 x 128) blocks + the vecmat partials
-    // + the lean group's scratch (M [128][256], s [128])
+// the partial slabs of a pass (see partial_floats) + the lean group's scratch (M [128][256], s [128])
+extern "C" long long scnerf_nerf_wgrad_workspace_floats(int n_chunks) {
     return partial_floats(n_chunks) + kLeanScratchFloats;
 }
