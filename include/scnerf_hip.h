@@ -677,6 +677,36 @@ int scnerf_ray_batch(int mode, unsigned long long seed, unsigned long long step,
                      int rank, int world, int white_bkgd, int64_t* coords, int64_t* select_inds, int64_t* image_idx,
                      float* target, void* stream);
 
+/* ------------------------------------------------------------------ skipping empty rays (forward-only rendering) --------- */
+
+/* Which rays of a chunk go on to the fine stage.  acc [n] = the coarse stage's acc_map; tau in [0, 1).  Ray i is SKIPPED iff
+ * acc[i] <= tau, so a NaN is live.  Outputs: live_idx [n] int32 -- its first n_live entries are the live rays in ascending
+ * order (the rest is not written); slot_of [n] int32 -- a live ray's position in that list, -1 for a skipped ray;
+ * n_live -- stored to *n_live_dev (device memory) and, unless NULL, to *n_live_host, which must be page-locked host memory
+ * the device can reach (the host sizes the fine stage's launches from it, behind an event).  One workgroup, no atomics:
+ * the outputs are a function of the inputs alone.  n == 0 stores the two zeros.  SCN_EINVAL: n < 0 or n >= 2^31, tau outside
+ * [0, 1), a NULL array with n > 0, NULL n_live_dev, n_live_host not page-locked. */
+int scnerf_ray_compact(const float* acc, float tau, int* live_idx, int* slot_of, int* n_live_dev, int* n_live_host,
+                       long long n, void* stream);
+
+/* dst[j, :] = src[live_idx[j], :] for j < n_live: rows of w >= 1 floats (rays, z_vals, weights, the per-ray draws), src
+ * [n_src, w], dst [n_live, w].  An index outside [0, n_src) is not followed: its row is zero.  n_live == 0 is a no-op.
+ * SCN_EINVAL: w < 1, n_live > n_src, n_src >= 2^31, a NULL array. */
+int scnerf_ray_rows_gather(const float* src, const int* live_idx, float* dst, long long n_live, int w, long long n_src,
+                           void* stream);
+
+/* The fine stage's outputs on the n_live live rays -> outputs for all n rays, every element written (no memset needed).
+ * Ray i with s = slot_of[i] in [0, n_live): rgb_map / disp_map / acc_map / depth_map / z_std [i] and the rows raw [i, s_tot, 4],
+ * z_vals [i, s_tot], z_samples [i, s_fine] are row s of the *_l arrays.  Any other ray (skipped): rgb_map = rgb0,
+ * disp_map = disp0, acc_map = acc0, depth_map = depth0 (the coarse stage's, [n, ...]), z_std = 0 and zero rows.
+ * n == 0 is a no-op; with n_live == 0 the *_l arrays may be NULL.  SCN_EINVAL: n_live > n, n >= 2^31, s_fine outside
+ * [1, s_tot], a NULL array, raw or raw_l not 16-byte aligned. */
+int scnerf_ray_expand(const int* slot_of, long long n, long long n_live, int s_tot, int s_fine, const float* rgb_l,
+                      const float* disp_l, const float* acc_l, const float* depth_l, const float* z_std_l, const float* raw_l,
+                      const float* z_vals_l, const float* z_samples_l, const float* rgb0, const float* disp0,
+                      const float* acc0, const float* depth0, float* rgb_map, float* disp_map, float* acc_map,
+                      float* depth_map, float* z_std, float* raw, float* z_vals, float* z_samples, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

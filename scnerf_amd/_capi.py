@@ -107,6 +107,12 @@ PROTOTYPES = {
     # world, white_bkgd, coords, select_inds, image_idx, target
     "scnerf_ray_batch": [I, ctypes.c_ulonglong, ctypes.c_ulonglong, P, I, I, I, LL, LL, P, I, I, LL, LL, LL, LL, LL, I, I, I,
                          P, P, P, P, P],
+    # skipping empty rays: acc, tau, live_idx, slot_of, n_live (device word, pinned host word), n
+    "scnerf_ray_compact": [P, F, P, P, P, P, LL, P],
+    # src, live_idx, dst, n_live, row floats, n_src
+    "scnerf_ray_rows_gather": [P, P, P, LL, I, LL, P],
+    # slot_of, n, n_live, s_tot, s_fine, eight live arrays, four coarse arrays, eight full-size outputs
+    "scnerf_ray_expand": [P, LL, LL, I, I] + [P] * 8 + [P] * 4 + [P] * 8 + [P],
 }
 
 

@@ -130,6 +130,13 @@ class RenderRaysFunction(torch.autograd.Function):
         wf_f, pl_f = (wf_c, pl_c) if fine_net is net_c else ops.network_packs(fine_net, flat_f, train, n)
         mx_f = ops.ChunkMaxima(n * tot, dev) if (train and resident) else None
         gd_f = guards.get("fine")
+        if not train and sf > 0 and ops.inference_skip_empty() is not None and n > 0:
+            # forward-only with ops.inference_skip_empty(tau): the fine stage on the rays the coarse stage found something on
+            out = RenderRaysFunction._fine_stage_on_live_rays(
+                ops.inference_skip_empty(), rays, z_c, w_c, u_dev, _c(noise_f), cfg.white_bkgd, wf_f, pl_f, gd_f,
+                (rgb_c, disp_c, acc_c, depth_c), sc, sf)
+            ctx.mark_non_differentiable(*out[5:])
+            return out[:5] + (rgb_c, disp_c, acc_c, depth_c) + out[5:]
         # (with the guard on, and on the one-product arithmetic, the three launches: the same numbers as the fused stage)
         if ops.fused_fine_stage() and gd_f is None and not fast and resident and sc == ops.COARSE_STAGE_SAMPLES and sf in ops.FINE_STAGE_IMPORTANCE and n > 0:
             # the whole fine stage -- inverse-cdf sampler, merge, network, compositing -- as one launch (opt-in: measured
@@ -147,6 +154,26 @@ class RenderRaysFunction(torch.autograd.Function):
         ctx.wb_f = (ctx.wb_c if fine_net is net_c else ops.pack_weights(flat_f, "bwd")) if train else None
         ctx.mark_non_differentiable(z_std, z_f, z_s)
         return (rgb_f, disp_f, acc_f, depth_f, raw_f, rgb_c, disp_c, acc_c, depth_c, z_std, z_f, z_s)
+
+    @staticmethod
+    def _fine_stage_on_live_rays(tau, rays, z_c, w_c, u, noise_f, white_bkgd, wf_f, pl_f, gd_f, coarse, sc, sf):
+        """The fine stage of a forward-only call under ops.inference_skip_empty(tau): compaction of the rays with
+        acc0 > tau (one host read: the count sizes the launches), the three launches on that batch, expansion.
+        -> (rgb_map, disp_map, acc_map, depth_map, raw, z_std, z_vals, z_samples) for every ray.  All rays live goes the same
+        way; none live launches nothing but the expansion."""
+        tot = sc + sf
+        live_idx, slot_of, n_live = ops.ray_compact(coarse[2], tau)
+        live = None
+        if n_live > 0:
+            rays_l, z_l, w_l = (ops.ray_rows_gather(t, live_idx, n_live) for t in (rays, z_c, w_c))
+            u_l = ops.ray_rows_gather(u, live_idx, n_live) if u.dim() == 2 else u
+            noise_l = ops.ray_rows_gather(noise_f, live_idx, n_live) if noise_f is not None else None
+            z_f, pts_f, z_s, z_std, _, _ = ops.fine_sample(rays_l, z_l, w_l, u_l)
+            raw_f = ops.mlp_fwd(pts_f, rays_l[:, 8:11], tot, wf_f, None, planes=pl_f, guard=gd_f).view(n_live, tot, 4)
+            rgb_f, disp_f, acc_f, _, depth_f = ops.composite_fwd(raw_f, z_f, rays_l, noise_l, white_bkgd, want_weights=False)
+            live = (rgb_f, disp_f, acc_f, depth_f, z_std, raw_f, z_f, z_s)
+        rgb, disp, acc, depth, z_std, raw, z_vals, z_samples = ops.ray_expand(slot_of, n_live, live, coarse, tot, sf)
+        return rgb, disp, acc, depth, raw, z_std, z_vals, z_samples
 
     @staticmethod
     def _stage_dgrad(stage, rays, spr, wbk, white_bkgd, g_rgb, g_disp, g_acc, g_depth, g_raw, d_rays, accumulate,

@@ -319,6 +319,123 @@ def inference_arithmetic(mode: Optional[str] = None) -> str:
     return _INFERENCE_ARITHMETIC(mode)
 
 
+class _FloatSwitch:
+    """_Switch's sibling for a threshold: a float in [lo, hi) -- kept as the fp32 value the kernels compare with -- or off
+    (None).  `switch(x)` sets it, `switch("off")` switches it off, `switch()` reads it; the preset comes from the
+    environment variable `env` ("off", empty or unset: off).  Anything else raises ValueError."""
+
+    def __init__(self, env, lo, hi, what):
+        self.lo, self.hi, self.what = lo, hi, what
+        preset = os.environ.get(env)
+        self.value = None if preset in (None, "", "off") else self._parse(preset, env)
+
+    def _parse(self, value, what):
+        try:
+            x = float(np.float32(float(value))) if not isinstance(value, bool) else None
+        except (TypeError, ValueError):
+            x = None
+        if x is None or not (self.lo <= x < self.hi):
+            raise ValueError("%s is \"off\" or a number in [%g, %g), not %r" % (what, self.lo, self.hi, value))
+        return x
+
+    def __call__(self, value=None):
+        if value is not None:
+            self.value = None if (isinstance(value, str) and value == "off") else self._parse(value, self.what)
+        return self.value
+
+
+_INFERENCE_SKIP_EMPTY = _FloatSwitch("SCNERF_INFER_SKIP_EMPTY", 0.0, 1.0, "inference_skip_empty")
+_SKIP_EMPTY_STATS = {"rays": 0, "skipped": 0}
+
+
+def inference_skip_empty(threshold=None) -> Optional[float]:
+    """Forward-only render_rays calls skip the fine pass of the rays the coarse pass found empty: a float tau in [0, 1)
+    switches it on, "off" (the default) off.  After the coarse stage of a chunk a ray with acc0 <= tau is SKIPPED (a NaN
+    acc0 is not); the live rays -- their rows of the ray batch, of the coarse depths and weights and of per-ray draws -- are
+    compacted, in ray order, into a shorter batch, the fine sampler, the fine network and the compositing run on that
+    batch in the arithmetic and guard mode in force (the three launches, also under fused_fine_stage), and the outputs
+    are expanded to the full batch: a live ray's are those of a switch-off call on the live rays alone, bit for bit; a
+    skipped ray returns the coarse stage's rgb_map = rgb0, disp_map = disp0, acc_map = acc0, depth_map = depth0, z_std = 0
+    and zero rows of raw, z_vals and z_samples.  What the coarse network does not see -- thin structures -- is lost on a
+    skipped ray: tau is the caller's trade-off.  Honoured by a forward-only render_rays call on the fused path with
+    N_importance > 0 (render_path, render_path_sharded, anything under torch.no_grad()); ignored by calls that track
+    gradients, the NeRF++ node, network queries and the opaque-callable path.
+    THE ONE HOST WAIT of the feature: the number of live rays sizes the fine stage's launches, so every chunk the host waits
+    on an event behind the compaction kernel and reads one 4-byte word from pinned memory -- the coarse stage of a chunk has
+    finished before its fine stage is enqueued (skip_empty_stats() re-uses these reads).
+    Without an argument: the threshold in force, None when off.  Environment preset: SCNERF_INFER_SKIP_EMPTY."""
+    return _INFERENCE_SKIP_EMPTY(threshold)
+
+
+def skip_empty_stats(reset: bool = False) -> dict:
+    """{"rays": rays compacted so far, "skipped": those of them skipped}: host-side sums of the counts ray_compact has
+    already read (no device access); `reset` zeroes them after the read."""
+    out = dict(_SKIP_EMPTY_STATS)
+    if reset:
+        _SKIP_EMPTY_STATS["rays"] = _SKIP_EMPTY_STATS["skipped"] = 0
+    return out
+
+
+def ray_compact(acc: Tensor, tau: float):
+    """acc [n] (the coarse stage's acc_map), tau -> (live_idx int32 [n], slot_of int32 [n], n_live): ray i is live unless
+    acc[i] <= tau; live_idx[:n_live] are the live rays ascending, slot_of[i] a live ray's position among them, -1 for a
+    skipped one (csrc/ray_compact.hip).  WAITS for the launch: n_live is read from a pinned word behind an event."""
+    _f(acc, "acc")
+    n = acc.numel()
+    both = torch.empty((2, n), dtype=torch.int32, device=acc.device)
+    count = torch.empty(1, dtype=torch.int32, device=acc.device)
+    # (CPU tensors: the interpreter build of the kernels under test, which runs the launch to its end)
+    host = torch.empty(1, dtype=torch.int32, device="cpu", pin_memory=acc.is_cuda)
+    st = _capi.load().scnerf_ray_compact(_p(acc), float(tau), _p(both[0]), _p(both[1]), _p(count), _p(host), n, _stream())
+    _capi.check(st, "scnerf_ray_compact")
+    if acc.is_cuda:
+        ev = torch.cuda.Event()
+        ev.record()
+        ev.synchronize()
+    n_live = int(host[0])
+    _SKIP_EMPTY_STATS["rays"] += n
+    _SKIP_EMPTY_STATS["skipped"] += n - n_live
+    return both[0], both[1], n_live
+
+
+def ray_rows_gather(src: Tensor, live_idx: Tensor, n_live: int) -> Tensor:
+    """src [n, w] -> [n_live, w]: the rows live_idx[:n_live]"""
+    _f(src, "src"), _chk(live_idx, torch.int32, "live_idx")
+    n, w = src.shape
+    if not 0 <= n_live <= live_idx.numel():
+        raise ValueError("n_live outside the index list")
+    dst = torch.empty((n_live, w), dtype=torch.float32, device=src.device)
+    st = _capi.load().scnerf_ray_rows_gather(_p(src), _p(live_idx), _p(dst), int(n_live), w, n, _stream())
+    _capi.check(st, "scnerf_ray_rows_gather")
+    return dst
+
+
+def ray_expand(slot_of: Tensor, n_live: int, live, coarse, s_tot: int, s_fine: int):
+    """live = (rgb, disp, acc, depth, z_std, raw, z_vals, z_samples) of the fine stage on the n_live live rays (None when
+    there is none), coarse = (rgb0, disp0, acc0, depth0) of all n rays -> the same eight tensors for n rays: a live ray's
+    row from `live`, a skipped ray's per-ray values from `coarse`, z_std = 0 and zero rows (one launch, no memset)."""
+    _chk(slot_of, torch.int32, "slot_of")
+    n, dev = slot_of.numel(), slot_of.device
+    if live is None:
+        if n_live:
+            raise ValueError("live rays without their fine-stage outputs")
+        live = (None,) * 8
+    sizes = [m * k for m in (int(n_live), n) for k in (3, 1, 1, 1, 1, 4 * s_tot, s_tot, s_fine)][:12]
+    for t_, size in zip(tuple(live) + tuple(coarse), sizes):
+        if t_ is not None and _f(t_, "ray_expand input").numel() != size:
+            raise ValueError("ray_expand: an input of %d floats where %d belong" % (t_.numel(), size))
+    rgb, disp, acc, depth, _ = _ray_outputs(n, 0, dev, want_weights=False)
+    z_std = torch.empty((n,), dtype=torch.float32, device=dev)
+    raw = torch.empty((n, s_tot, 4), dtype=torch.float32, device=dev)
+    z_vals = torch.empty((n, s_tot), dtype=torch.float32, device=dev)
+    z_samples = torch.empty((n, s_fine), dtype=torch.float32, device=dev)
+    st = _capi.load().scnerf_ray_expand(_p(slot_of), n, int(n_live), int(s_tot), int(s_fine), *[_p(t_) for t_ in live],
+                                        *[_p(t_) for t_ in coarse], _p(rgb), _p(disp), _p(acc), _p(depth), _p(z_std), _p(raw),
+                                        _p(z_vals), _p(z_samples), _stream())
+    _capi.check(st, "scnerf_ray_expand")
+    return rgb, disp, acc, depth, z_std, raw, z_vals, z_samples
+
+
 RESIDENT_GUARDS = ("off", "fallback", "report", "strict")
 # Off by default: on the headline step the fallback mode costs 1.4 - 1.5 % (medians of alternating runs in both orders,
 # profiles/r07_resident_guard.txt) -- over the half per cent a default may cost.
