@@ -707,6 +707,55 @@ int scnerf_ray_expand(const int* slot_of, long long n, long long n_live, int s_t
                       const float* acc0, const float* depth0, float* rgb_map, float* disp_map, float* acc_map,
                       float* depth_map, float* z_std, float* raw, float* z_vals, float* z_samples, void* stream);
 
+/* ------------------------------------------------------------------ the backward pass on the live samples ----------------- */
+
+/* A sample whose d_raw row [4] is all +-0 (noisy density <= 0: alpha = 0) contributes exact zeros to every gradient of the
+ * network.  scnerf_live_compact lists the others -- a sample is LIVE when any of its four words is non-zero with the sign bit
+ * ignored, so a NaN is live -- in ascending order: live_idx [padded n_samples] int32, xoff [padded n_samples] uint32 (byte
+ * offset (i >> 5) * 32768 + (i & 31) * 16 of sample i in a tile-native section of width 256, stored at entry
+ * 16 (k >> 4) + 2 (k & 7) + ((k >> 3) & 1) for compact sample k: the order the 256 x 256 weight-gradient kernel loads it in),
+ * d_raw_live [n_samples][4] (its first n_live rows are written) and the count, to *n_live_dev and, unless NULL, to
+ * *n_live_host, page-locked host memory the device can reach.  Entries of live_idx / xoff from n_live up to n_live padded to
+ * 128 are 0.  workspace: scnerf_live_compact_workspace_ints(n_samples) int32.  Two launches, no atomics: the outputs are a
+ * function of the input alone.  SCN_EINVAL: n_samples < 1, a NULL array, d_raw / d_raw_live not 16-byte or xoff not 8-byte
+ * aligned, n_live_host not page-locked; SCN_ENOSUP: n_samples > 2^22 - 128 (the offsets are 32 bits).
+ * scnerf_live_gather: what the data-gradient kernel reads for the compact batch -- masks_live, nine lane-native sections over
+ * n_live padded to 128 (16 bytes per lane: tile k >> 5, lanes (k & 31) and 32 + (k & 31), from the same places of sample
+ * live_idx[k] in `masks`, the mask sections behind a workspace of n_samples; zeros behind n_live), pts_live [n_live][pt_dims]
+ * and vd_live [n_live][3], the direction of ray live_idx[k] / samples_per_ray.  n_live == 0 is a no-op.
+ * scnerf_live_remap_maxima: amax_dst[row][c] = the largest amax_src[row][o] over the source chunks o (chunk_src samples each)
+ * that the live samples of compact chunk c (chunk_dst samples each) come from -- and source chunk 0 as well for a chunk that
+ * reaches past n_live, where the padding entries name sample 0; rows <= 64.
+ * scnerf_mlp_bwd_h3_masks: scnerf_mlp_bwd_h3_lean with the masks given by their own pointer (no workspace); a guard record has one flag per
+ * 128 samples of the compact batch.
+ * scnerf_nerf_wgrad_h3_live: the weight-gradient group of the pass over the live samples -- grads_live, n_live,
+ * n_chunks_live and both maxima tables belong to the compact batch, save / d_raw / n_samples_src to the forward; every GEMM
+ * gathers its X through live_idx / xoff, vecmat and rows4 stay dense in n_chunks_src >= n_chunks_live workgroups (alpha_linear
+ * and rgb_linear keep the dense group's bits); workspace: scnerf_nerf_wgrad_workspace_floats(n_chunks_src); flat_params NULL:
+ * the full group, else the lean one.  Half arithmetic and all three tables required (SCN_EINVAL otherwise). */
+long long scnerf_live_compact_workspace_ints(long long n_samples);
+int scnerf_live_compact(const float* d_raw, long long n_samples, int* workspace, int* live_idx, unsigned* xoff,
+                        float* d_raw_live, int* n_live_dev, int* n_live_host, void* stream);
+int scnerf_live_gather(const int* live_idx, long long n_live, long long n_samples, const unsigned* masks, const float* pts,
+                       int pt_dims, const float* viewdirs, int vd_stride, int samples_per_ray, unsigned* masks_live,
+                       float* pts_live, float* vd_live, void* stream);
+/* dst [n][w] = 0, then row live_idx[k] = src row k for k < n_live (the input gradient of the compact batch back in sample
+ * order; an index outside [0, n) is not followed).  SCN_EINVAL: n_live > n, w < 1, a NULL array. */
+int scnerf_live_scatter_rows(const float* src, const int* live_idx, float* dst, long long n_live, int w, long long n,
+                             void* stream);
+int scnerf_live_remap_maxima(const int* live_idx, long long n_live, const float* amax_src, int n_chunks_src,
+                             long long chunk_src, float* amax_dst, int n_chunks_dst, long long chunk_dst, int rows, void* stream);
+int scnerf_mlp_bwd_h3_masks(int pt_dims, const float* d_raw, const float* pts, const float* viewdirs, int vd_stride,
+                            int samples_per_ray, const float* wpacked_bwd, const short* stream_bwd, const float* scales,
+                            const unsigned* masks, float* grads, float* d_pts, float* d_views, long long n_samples,
+                            float* chunk_amax, int n_chunks, long long chunk_samples, int* guard_flags, int* guard_any,
+                            float* guard_report, int lean, void* stream);
+int scnerf_nerf_wgrad_h3_live(int pt_dims, const float* save, long long n_samples_src, int n_chunks_src,
+                              const float* grads_live, const float* d_raw, const int* live_idx, const unsigned* xoff,
+                              long long n_live, int n_chunks_live, float* workspace, float* flat_grad, int accumulate,
+                              const float* amax_x_live, const float* amax_z_live, const float* scales, const float* flat_params,
+                              void* ev_before, void* ev_after, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -113,6 +113,18 @@ PROTOTYPES = {
     "scnerf_ray_rows_gather": [P, P, P, LL, I, LL, P],
     # slot_of, n, n_live, s_tot, s_fine, eight live arrays, four coarse arrays, eight full-size outputs
     "scnerf_ray_expand": [P, LL, LL, I, I] + [P] * 8 + [P] * 4 + [P] * 8 + [P],
+    # the backward pass on the live samples: d_raw, n, workspace, live_idx, xoff, d_raw_live, n_live (device, pinned host)
+    "scnerf_live_compact": [P, LL, P, P, P, P, P, P, P],
+    # live_idx, n_live, n, masks, pts, pt_dims, viewdirs, vd_stride, samples_per_ray, masks_live, pts_live, vd_live
+    "scnerf_live_gather": [P, LL, LL, P, P, I, P, I, I, P, P, P, P],
+    # live_idx, n_live, amax_src, n_chunks_src, chunk_src, amax_dst, n_chunks_dst, chunk_dst, rows
+    "scnerf_live_remap_maxima": [P, LL, P, I, LL, P, I, LL, I, P],
+    # src, live_idx, dst, n_live, row floats, n
+    "scnerf_live_scatter_rows": [P, P, P, LL, I, LL, P],
+    "scnerf_mlp_bwd_h3_masks": [I, P, P, P, I, I, P, P, P, P, P, P, P, LL, P, I, LL, P, P, P, I, P],
+    # pt_dims, save, n_src, n_chunks_src, grads_live, d_raw, live_idx, xoff, n_live, n_chunks_live, workspace, flat_grad,
+    # accumulate, amax_x_live, amax_z_live, scales, flat_params, two events
+    "scnerf_nerf_wgrad_h3_live": [I, P, LL, I, P, P, P, P, LL, I, P, P, I, P, P, P, P, P, P, P],
 }
 
 
@@ -123,6 +135,7 @@ SIZE_FUNCS = {"scnerf_mlp_save_floats": [I, LL], "scnerf_mlp_grad_floats": [LL],
               "scnerf_h3_scale_floats": [],
               "scnerf_wgrad_chunk_samples": [LL, I],
               "scnerf_camera_bwd_workspace_floats": [I],
+              "scnerf_live_compact_workspace_ints": [LL],
               "scnerf_image_metrics_workspace_floats": [I, I, I, I, I]}
 
 

@@ -7,10 +7,13 @@
 //
 // Gradient of: NeRF.forward + Embedder + run_network
 //   /root/reference NeRF/run_nerf_helpers.py:105-128, :24-72, NeRF/create_nerf.py:18-32 (what autograd derives).
+#include <cstdint>
+
 #include <scn_wave.h>
 
 #include "launch.h"
 #include "mlp_bwd_h3_api.h"
+#include "mlp_common.h"
 #include "scnerf_hip.h"
 
 extern "C" int scnerf_mlp_bwd_h3_lean(int pt_dims, const float* d_raw, const float* pts, const float* viewdirs,
@@ -29,6 +32,23 @@ extern "C" int scnerf_mlp_bwd_h3_lean(int pt_dims, const float* d_raw, const flo
     const scn::h3b::ChunkMaxima cm{chunk_amax, n_chunks, lean != 0, (long)chunk_samples, {guard_flags, guard_any, guard_report}};
     return pt_dims == 3 ? scn::h3b::bwd_h3_pd3(d_raw, pts, viewdirs, vd_stride, samples_per_ray, wpacked_bwd, stream_bwd, scales, save, grads, d_pts, d_views, n_samples, cm, st)
                         : scn::h3b::bwd_h3_pd4(d_raw, pts, viewdirs, vd_stride, samples_per_ray, wpacked_bwd, stream_bwd, scales, save, grads, d_pts, d_views, n_samples, cm, st);
+}
+
+// The same launch with the ReLU masks in a buffer of their own (nine lane-native sections over padded n_samples, as
+// behind the row sections of a workspace): the batch of live samples of live_compact.hip has no workspace.  The kernel
+// reads nothing but the masks through `save`, at save + kSavePerSample * Ppad: it is handed the address that puts them
+// there.  A guard record here has one flag per 128 samples of THIS batch.
+extern "C" int scnerf_mlp_bwd_h3_masks(int pt_dims, const float* d_raw, const float* pts, const float* viewdirs,
+                                       int vd_stride, int samples_per_ray, const float* wpacked_bwd, const short* stream_bwd,
+                                       const float* scales, const unsigned* masks, float* grads, float* d_pts, float* d_views,
+                                       long long n_samples, float* chunk_amax, int n_chunks, long long chunk_samples,
+                                       int* guard_flags, int* guard_any, float* guard_report, int lean, void* stream) {
+    SCN_RETURN_IF(!masks || n_samples < 0 || (pt_dims != 3 && pt_dims != 4), SCN_EINVAL);
+    const long long per_sample = pt_dims == 3 ? scn::mlp::Var<3>::kSavePerSample : scn::mlp::Var<4>::kSavePerSample;
+    const uintptr_t base = reinterpret_cast<uintptr_t>(masks) - (uintptr_t)(per_sample * scn::mlp::padded_samples((long)n_samples)) * sizeof(float);
+    return scnerf_mlp_bwd_h3_lean(pt_dims, d_raw, pts, viewdirs, vd_stride, samples_per_ray, wpacked_bwd, stream_bwd, scales,
+                                  reinterpret_cast<const float*>(base), grads, d_pts, d_views, n_samples, chunk_amax, n_chunks,
+                                  chunk_samples, guard_flags, guard_any, guard_report, lean, stream);
 }
 
 extern "C" int scnerf_mlp_bwd_h3_guarded(int pt_dims, const float* d_raw, const float* pts, const float* viewdirs,

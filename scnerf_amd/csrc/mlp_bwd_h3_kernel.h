@@ -167,6 +167,9 @@ __global__ __launch_bounds__(kThreads, 1) void mlp_bwd_h3_kernel(
     auto section = [&](int offset, int width) {
         return uniform_global_rw(grads + (long)offset * Ppad + wave_tile * (32L * width));
     };
+    // THE ONLY read through `save`: the mask sections behind the row sections.  scnerf_mlp_bwd_h3_masks (mlp_bwd_h3.hip)
+    // relies on that -- for a batch without a workspace it passes the address that makes this sum its mask buffer, which
+    // lies outside any allocation.  Whoever reads anything else through `save` here must give the masks their own argument.
     auto load_gate = [&](int sect) {
         const unsigned* base = reinterpret_cast<const unsigned*>(save + (long)V::kSavePerSample * Ppad);
         return load_at<u32x4>(uniform_global(base + ((long)sect * (Ppad / 32) + wave_tile) * 256), w.lane16);

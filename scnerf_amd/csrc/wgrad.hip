@@ -541,7 +541,9 @@ int launch_wgrad256(const wg256::Args& a, int G, hipStream_t stream) {
 }
 
 // the same GEMMs on three fp16 products (wgrad256_half.h): needs the chunk maxima of both operands, [job][chunk]
-int launch_wgrad256_half(const wg256::Args& a, int G, const float* amax_a, const float* amax_b, hipStream_t stream) {
+// xoff (or nullptr): the samples are the live ones of a larger pass -- every job's X is gathered through the table
+int launch_wgrad256_half(const wg256::Args& a, int G, const float* amax_a, const float* amax_b, hipStream_t stream,
+                         const unsigned* xoff = nullptr) {
     wg256h::Args h;
     for (int j = 0; j < a.n_jobs; ++j) h.job[j] = a.job[j];
     h.n_jobs = a.n_jobs;
@@ -549,6 +551,13 @@ int launch_wgrad256_half(const wg256::Args& a, int G, const float* amax_a, const
     h.chunk = a.chunk;
     h.amax_a = amax_a;
     h.amax_b = amax_b;
+    h.xoff = xoff;
+    if (xoff) {
+        SCN_LDS_OPT_IN((wg256h::wgrad256_half_kernel<wg256h::kGatherX>), wg256h::kLdsBytes);
+        hipLaunchKernelGGL((wg256h::wgrad256_half_kernel<wg256h::kGatherX>), dim3(G, a.n_jobs), dim3(wg256h::kThreads),
+                           wg256h::kLdsBytes, stream, h);
+        return scn_launch_status();
+    }
     SCN_LDS_OPT_IN((wg256h::wgrad256_half_kernel<0>), wg256h::kLdsBytes);
     hipLaunchKernelGGL((wg256h::wgrad256_half_kernel<0>), dim3(G, a.n_jobs), dim3(wg256h::kThreads), wg256h::kLdsBytes,
                        stream, h);
@@ -570,6 +579,14 @@ template <int NA, int NB, bool B_ROWMAJOR, int WB2 = 0>
 int launch_wgrad_half_narrow(const wgnh::Args& a, int G, hipStream_t stream, int jobs = 1) {
     SCN_LDS_OPT_IN((wgnh::wgrad_half_narrow_kernel<NA, NB, B_ROWMAJOR, WB2>), wgnh::kLdsBytes);
     hipLaunchKernelGGL((wgnh::wgrad_half_narrow_kernel<NA, NB, B_ROWMAJOR, WB2>), dim3(G, jobs), dim3(wgnh::kThreads), wgnh::kLdsBytes, stream, a);
+    return scn_launch_status();
+}
+
+// the same launch over the live samples of a larger pass: X (and the second X operand) gathered through a.live_idx
+template <int NA, int NB, bool B_ROWMAJOR, int WB2 = 0>
+int launch_wgrad_half_narrow_live(const wgnh::Args& a, int G, hipStream_t stream, int jobs = 1) {
+    SCN_LDS_OPT_IN((wgnh::wgrad_half_narrow_kernel<NA, NB, B_ROWMAJOR, WB2, true>), wgnh::kLdsBytes);
+    hipLaunchKernelGGL((wgnh::wgrad_half_narrow_kernel<NA, NB, B_ROWMAJOR, WB2, true>), dim3(G, jobs), dim3(wgnh::kThreads), wgnh::kLdsBytes, stream, a);
     return scn_launch_status();
 }
 
@@ -656,7 +673,7 @@ struct NarrowScales {
 wgnh::Args narrow_args(const float* dz, const float* x, const Slab& out, const Samples& c, const NarrowScales& ns) {
     const wgnh::Bound none{nullptr, nullptr, nullptr};
     return wgnh::Args{dz, x, out.w, out.b, c.P, c.Ppad, c.chunk, ns.a, ns.b, ns.n_coarse, ns.coarse_chunk,
-                      nullptr, nullptr, none, nullptr, nullptr, nullptr, none};
+                      nullptr, nullptr, none, nullptr, nullptr, nullptr, none, nullptr};
 }
 wgt::Args tiles_args(const float* dz, const float* x, const Slab& out, const Samples& c) {
     return wgt::Args{dz, x, out.w, out.b, c.P, c.Ppad, c.chunk};
@@ -831,10 +848,18 @@ struct PassBuffers {
 // lean_params (the flat parameter buffer of the network that ran the pass): the LEAN group for workspaces whose
 // feature / d feature sections were not stored -- no feature_linear job (seven in the big launch, same chunking: the
 // other gradients stay bit-identical), the views layer's narrow GEMM on act7 into scratch, wgrad_lean_finish_kernel.
+// live (idx != nullptr): the pass runs on the LIVE samples of a larger one (live_compact.hip).  `grads`, P, the chunks
+// and both maxima tables belong to the compact batch; `save` and `d_raw` are the dense ones of the P_src samples of the
+// forward.  Every GEMM gathers its X through idx / xoff; vecmat and rows4, which read only X and d_raw, stay dense over
+// P_src in n_chunks_src workgroups (alpha_linear and rgb_linear keep the dense group's bits); the workspace is the one
+// of n_chunks_src >= n_chunks.
+struct LiveSamples { const int* idx; const unsigned* xoff; long long P_src; int n_chunks_src; };
+constexpr long long kLiveMaxSamples = (1LL << 22) - 128;       // 1 KB per sample and 256-wide section: offsets below 2^32
 struct PassOptions {
     const float* amax_x; const float* amax_z; const float* scales;
     hipEvent_t ev_before, ev_after;
     const float* lean_params;
+    LiveSamples live;
 };
 
 // A pass lays out its slabs and reduction jobs first, in the order of the flat gradient, then launches: layer 0 with the skip
@@ -849,15 +874,19 @@ int nerf_wgrad(const PassBuffers& io, const PassOptions& o) {
     const bool half_big = o.amax_x && o.amax_z && wgrad_arithmetic() == 1;
     const bool half_narrow = half_big && o.scales;
     SCN_RETURN_IF(lean && !half_narrow, SCN_EINVAL);     // (a lean workspace has no feature sections for the full group)
+    const bool live = o.live.idx != nullptr;
+    SCN_RETURN_IF(live && (!half_narrow || !o.live.xoff || o.live.P_src < io.P || o.live.n_chunks_src < io.n_chunks), SCN_EINVAL);
     const int nc = io.n_chunks, nb = big_chunks(nc);
+    const int nc_src = live ? o.live.n_chunks_src : nc;
     const Samples fine = cut(io.P, nc), coarse = cut(io.P, nb);
-    auto sv = [&](int sec) { return io.save + (long long)sec * fine.Ppad; };
+    const Samples src = live ? cut(o.live.P_src, nc_src) : fine;       // what `save` and `d_raw` cover
+    auto sv = [&](int sec) { return io.save + (long long)sec * src.Ppad; };
     auto gr = [&](int sec) { return io.grads + (long long)sec * fine.Ppad; };
     auto act = [&](int l) { return sv(kSaveAct + 256 * l); };
     auto dz = [&](int l) { return gr(kGradDz + 256 * l); };
     auto zrow = [&](int r) { return wgnh::Bound{o.amax_z + (long)r * nb, nullptr, nullptr}; };
     float* const g = io.g;
-    float* const scratch = io.workspace + lean_scratch_offset(nc);
+    float* const scratch = io.workspace + lean_scratch_offset(nc_src);
     hipStream_t st = io.st;
 
     Partials parts{io.workspace, scratch};
@@ -877,7 +906,7 @@ int nerf_wgrad(const PassBuffers& io, const PassOptions& o) {
     };
     auto trunk = [&](int l, int col0) { return Target{g + V::trunk_w(l), l == 5 ? SK : 256, col0, 256, 256, g + V::trunk_b(l)}; };
 
-    float* const vm = parts.take(vecmat_ws_floats(nc));           // [G][257]: the vecmat partials
+    float* const vm = parts.take(vecmat_ws_floats(nc_src));       // [G][257]: the vecmat partials
     SCN_RETURN_IF(!vm, SCN_EINVAL);
     Slab s_l0, s_skip;
     SCN_TRY(plan(Tile{nc, 256, EW, true}, Target{g + V::kW0, IN, 0, 256, IN, g + V::kB0}, &s_l0));
@@ -892,16 +921,18 @@ int nerf_wgrad(const PassBuffers& io, const PassOptions& o) {
     if (half_narrow) {
         wgnh::Args both = narrow_args(dz(0), sv(kSaveEpts), s_l0, fine, NarrowScales{zrow(9), zrow(10), nb, coarse.chunk});
         both.A_y1 = dz(5); both.part_w_y1 = s_skip.w; both.part_b_y1 = nullptr; both.a_y1 = zrow(4);
-        SCN_TRY((launch_wgrad_half_narrow<256, EW, true>(both, nc, st, 2)));
+        both.live_idx = o.live.idx;
+        SCN_TRY(live ? (launch_wgrad_half_narrow_live<256, EW, true>(both, nc, st, 2))
+                     : (launch_wgrad_half_narrow<256, EW, true>(both, nc, st, 2)));
     } else {
         SCN_TRY((launch_wgrad_tiles<256, EW, true>(tiles_args(dz(0), sv(kSaveEpts), s_l0, fine), nc, st)));
         SCN_TRY((launch_wgrad_tiles<256, EW, true>(tiles_args(dz(5), sv(kSaveEpts), without_bias(s_skip), fine), nc, st)));
     }
     // alpha_linear (one output row) = d sigma^T . act7 with d sigma = d_raw[:, 3]: the 256 sums and the bias sum as two jobs
-    hipLaunchKernelGGL(vecmat_kernel, dim3(nc), dim3(kThreads), 0, st, act(7), io.d_raw + 3, 4, fine.P, fine.Ppad / 32, vm);
+    hipLaunchKernelGGL(vecmat_kernel, dim3(nc_src), dim3(kThreads), 0, st, act(7), io.d_raw + 3, 4, src.P, src.Ppad / 32, vm);
     SCN_TRY(scn_launch_status());
-    SCN_TRY(red.push(Slab{vm, nullptr}, Tile{nc, 1, 257, false}, Target{g + V::kWA, 256, 0, 1, 256, nullptr}));
-    SCN_TRY(red.push(Slab{vm + 256, nullptr}, Tile{nc, 1, 257, false}, Target{g + V::kBA, 1, 0, 1, 1, nullptr}));
+    SCN_TRY(red.push(Slab{vm, nullptr}, Tile{nc_src, 1, 257, false}, Target{g + V::kWA, 256, 0, 1, 256, nullptr}));
+    SCN_TRY(red.push(Slab{vm + 256, nullptr}, Tile{nc_src, 1, 257, false}, Target{g + V::kBA, 1, 0, 1, 1, nullptr}));
     // views layer: X = [feature | encoded direction].  Half arithmetic: one narrow launch with the direction as second X
     // operand (WB2 = 32), dZ is read (and cut) once; otherwise wgrad_tiles<128, 256> and the generic 128 x 64 kernel
     const Target views_dir{g + V::kWV, 283, 256, 128, 27, nullptr};
@@ -918,7 +949,9 @@ int nerf_wgrad(const PassBuffers& io, const PassOptions& o) {
         wgnh::Args t = narrow_args(gr(kGradDzv), lean ? act(7) : sv(kSaveFeat), s_feat, fine,
                                    NarrowScales{zrow(8), lean ? b_act7 : b_feat, nb, coarse.chunk});
         t.B2 = sv(kSaveEviews); t.part_w2 = s_dir.w; t.b2 = zrow(11);
-        SCN_TRY((launch_wgrad_half_narrow<128, 256, false, 32>(t, nc, st)));
+        t.live_idx = o.live.idx;
+        SCN_TRY(live ? (launch_wgrad_half_narrow_live<128, 256, false, 32>(t, nc, st))
+                     : (launch_wgrad_half_narrow<128, 256, false, 32>(t, nc, st)));
     } else {
         SCN_TRY(plan(Tile{nc, 128, 256, true}, Target{g + V::kWV, 283, 0, 128, 256, g + V::kBV}, &s_feat));
         SCN_TRY(plan(Tile{nc, 128, 64, true}, views_dir, &s_dir));
@@ -929,11 +962,11 @@ int nerf_wgrad(const PassBuffers& io, const PassOptions& o) {
     // rgb_linear: dZ = d_raw[:, 0:3] (row-major), X = hidden of the views layer
     // (rows4_kernel: the hidden layer is read once at the HBM rate; the general kernel pads three rows to a 64-row tile)
     Slab s_rgb;
-    SCN_TRY(plan(Tile{nc, 4, 128, true}, Target{g + V::kWRGB, 128, 0, 3, 128, g + V::kBRGB}, &s_rgb));
-    hipLaunchKernelGGL(rows4_kernel, dim3(nc), dim3(kThreads), 0, st, sv(kSaveHv), io.d_raw, fine.P, fine.Ppad / 32, s_rgb.w, s_rgb.b);
+    SCN_TRY(plan(Tile{nc_src, 4, 128, true}, Target{g + V::kWRGB, 128, 0, 3, 128, g + V::kBRGB}, &s_rgb));
+    hipLaunchKernelGGL(rows4_kernel, dim3(nc_src), dim3(kThreads), 0, st, sv(kSaveHv), io.d_raw, src.P, src.Ppad / 32, s_rgb.w, s_rgb.b);
     SCN_TRY(scn_launch_status());
     if (o.ev_before) SCN_HIP(hipEventRecord(o.ev_before, st));
-    SCN_TRY(half_big ? launch_wgrad256_half(big, nb, o.amax_z, o.amax_x, st) : launch_wgrad256(big, nb, st));
+    SCN_TRY(half_big ? launch_wgrad256_half(big, nb, o.amax_z, o.amax_x, st, o.live.xoff) : launch_wgrad256(big, nb, st));
     if (o.ev_after) SCN_HIP(hipEventRecord(o.ev_after, st));
     // one launch finishes every GEMM (fixed-order sums: deterministic)
     hipLaunchKernelGGL(wgrad_reduce_multi_kernel, dim3(red.blocks), dim3(256), 0, st, red.jobs);
@@ -974,6 +1007,22 @@ extern "C" int scnerf_nerf_wgrad_h3_lean(int pt_dims, const float* save, const f
     SCN_RETURN_IF(!amax_x || !amax_z || !scales || !flat_params || wgrad_arithmetic() != 1, SCN_EINVAL);
     return nerf_wgrad_entry(pt_dims, PassBuffers{save, grads, d_raw, n_samples, n_chunks, workspace, flat_grad, accumulate, (hipStream_t)stream},
                             PassOptions{amax_x, amax_z, scales, (hipEvent_t)ev_before, (hipEvent_t)ev_after, flat_params});
+}
+
+// the group over the live samples of a pass (include/scnerf_hip.h): the half arithmetic and all three tables required;
+// flat_params NULL: the full group, else the lean one
+extern "C" int scnerf_nerf_wgrad_h3_live(int pt_dims, const float* save, long long n_samples_src, int n_chunks_src,
+                                         const float* grads_live, const float* d_raw, const int* live_idx,
+                                         const unsigned* xoff, long long n_live, int n_chunks_live, float* workspace,
+                                         float* flat_grad, int accumulate, const float* amax_x_live, const float* amax_z_live,
+                                         const float* scales, const float* flat_params, void* ev_before, void* ev_after,
+                                         void* stream) {
+    SCN_RETURN_IF(!amax_x_live || !amax_z_live || !scales || !live_idx || !xoff || wgrad_arithmetic() != 1, SCN_EINVAL);
+    SCN_RETURN_IF(n_live < 1 || n_live > n_samples_src || n_chunks_live < 1 || n_chunks_live > n_chunks_src, SCN_EINVAL);
+    SCN_RETURN_IF(n_samples_src > kLiveMaxSamples, SCN_ENOSUP);      // (the byte offsets of a 256-wide section fit 32 bits)
+    return nerf_wgrad_entry(pt_dims, PassBuffers{save, grads_live, d_raw, n_live, n_chunks_live, workspace, flat_grad, accumulate, (hipStream_t)stream},
+                            PassOptions{amax_x_live, amax_z_live, scales, (hipEvent_t)ev_before, (hipEvent_t)ev_after, flat_params,
+                                        LiveSamples{live_idx, xoff, n_samples_src, n_chunks_src}});
 }
 
 extern "C" int scnerf_wgrad_arithmetic(int mode) {

@@ -62,7 +62,14 @@ struct Args {
     long chunk;            // samples per workgroup (multiple of 32)
     const float* amax_a;   // [n_jobs][gridDim.x] largest |dZ| of the chunk
     const float* amax_b;   // [n_jobs][gridDim.x] largest |X| of the chunk
+    // FLAGS & kGatherX: the samples are the LIVE ones of a larger pass (live_compact.hip).  dZ is compact; the X sections
+    // are the dense ones of the forward, and sample k of the compact batch has its 16-byte pieces at byte offset
+    // xoff[..] + 512 * (4-feature group) of its section.  The table is in loader order: per 16-sample slab the two
+    // samples (ml, ml + 8) of a lane adjacent, entry 16 (k >> 4) + 2 (k & 7) + ((k >> 3) & 1) -- one 8-byte load per lane
+    // and slab -- and covers Ppad entries (those behind the last live sample point at sample 0: their dZ rows are zero).
+    const unsigned* xoff;
 };
+constexpr int kGatherX = 1;
 
 // 2^k with bound 2^k < 2^13 (as mlp_h3.h's scale_for)
 __device__ __forceinline__ float scale_for(float bound) {
@@ -144,6 +151,18 @@ __global__ __launch_bounds__(kThreads, 1) void wgrad256_half_kernel(Args a) {
     const int rd_b = rd_row * kRowEl + 2 * kPlane + 128 * wk + rd_col;
 
     f32x4 raw[2][8];       // [set][operand * 4 + j * 2 + mh]
+    // gathered X: the offsets of the lane's two samples of the slab the set loads next.  They are fetched right behind the
+    // last operand load of a slab, two slabs before their use: by then every load in front of them has been waited for
+    // by the cut anyway, so the operand stream's vmcnt waits keep their places.
+    constexpr bool GATHER = (FLAGS & kGatherX) != 0;
+    u32x2 xo[2] = {u32x2{0u, 0u}, u32x2{0u, 0u}};
+    auto load_offsets = [&](auto set_tag, int s) {
+        constexpr int SET = decltype(set_tag)::value;
+        if constexpr (GATHER) {
+            s = min(s, n_slab - 1);
+            xo[SET] = *reinterpret_cast<const u32x2*>(a.xoff + p_begin + (long)s * 16 + ml * 2);
+        }
+    };
     auto load_slab = [&](auto set_tag, int s, int first, int count) {
         constexpr int SET = decltype(set_tag)::value;
         s = min(s, n_slab - 1);
@@ -154,6 +173,13 @@ __global__ __launch_bounds__(kThreads, 1) void wgrad256_half_kernel(Args a) {
         for (int x = 0; x < 8; ++x) {
             if (x < first || x >= first + count) continue;
             const int o = x >> 2, j = (x >> 1) & 1, mh = x & 1;
+            if constexpr (GATHER) {
+                if (o) {
+                    const char* bj = reinterpret_cast<const char*>(J.B) + j * 16384;
+                    raw[SET][x] = load_stream(reinterpret_cast<const f32x4*>(bj + (xo[SET][mh] + (unsigned)fg0 * 512u)));
+                    continue;
+                }
+            }
             raw[SET][x] = load_stream(reinterpret_cast<const f32x4*>((o ? bB : bA) + j * 4096 + mh * 32));
         }
     };
@@ -221,6 +247,7 @@ __global__ __launch_bounds__(kThreads, 1) void wgrad256_half_kernel(Args a) {
             // ---- fillers ----
             if constexpr (KIND < 2) cut_step(Set{}, fil, std::integral_constant<int, G / 6>{}, std::integral_constant<int, G % 6>{});
             if constexpr (KIND == 0 && G % 6 == 5) load_slab(Set{}, s + 4, G / 6, 1);
+            if constexpr (KIND == 0 && G == 47) load_offsets(Set{}, s + 6);
             constexpr int NR = reads_in_slot(G), K0 = reads_before(G);
             auto one_read = [&](auto k_tag) {
                 constexpr int IT = read_item(decltype(k_tag)::value), PL = IT >> 3, PC = IT & 7;
@@ -262,12 +289,18 @@ __global__ __launch_bounds__(kThreads, 1) void wgrad256_half_kernel(Args a) {
         whole(std::integral_constant<int, 4>{}); whole(std::integral_constant<int, 5>{});
         whole(std::integral_constant<int, 6>{}); whole(std::integral_constant<int, 7>{});
     };
+    load_offsets(S0{}, 0);
+    load_offsets(S1{}, 1);
     load_slab(S0{}, 0, 0, 8);
     load_slab(S1{}, 1, 0, 8);
+    load_offsets(S0{}, 2);
+    load_offsets(S1{}, 3);
     cut_whole(S0{}, 0);
     load_slab(S0{}, 2, 0, 8);
     cut_whole(S1{}, 1);
     load_slab(S1{}, 3, 0, 8);
+    load_offsets(S0{}, 4);
+    load_offsets(S1{}, 5);
     sync();
     read_plane(Ah[0], 0, rd_a, 0);
     read_plane(Al[0], 0, rd_a, 1);

@@ -81,6 +81,11 @@ struct Args {
     float* part_w_y1;
     float* part_b_y1;
     Bound a_y1;
+    // LIVE: the samples are the live ones of a larger pass (live_compact.hip).  dZ, P, Ppad and the chunks are the compact
+    // batch's; B (and B2) are the dense operands of the forward, and compact sample k reads the row / tile column of sample
+    // live_idx[k] (Ppad entries; those behind the last live sample name sample 0: their dZ rows are zero, and a row-major
+    // operand stages zeros there anyway).
+    const int* live_idx;
 };
 
 // where the 4-feature group fg of an operand sits in its 256-position region of an LDS row (wgrad256_half.h's image)
@@ -88,9 +93,14 @@ __device__ __forceinline__ int region_pos(int fg) {
     return 128 * (fg >> 5) + 16 * ((fg >> 3) & 3) + 64 * ((fg & 7) >> 2) + 4 * (fg & 3);
 }
 
-template <int WA, int WB, bool B_ROWMAJOR, int WB2 = 0>
+template <int WA, int WB, bool B_ROWMAJOR, int WB2 = 0, bool LIVE = false>
 __global__ __launch_bounds__(kThreads, (WA == 256 && WB == 64 && WB2 == 0) ? 2 : 1) void wgrad_half_narrow_kernel(Args a) {
     if constexpr (!(WA == 256 && WB == 64 && WB2 == 0)) claim_whole_register_file();     // the one-wave-per-SIMD shapes admit no guest (scn_wave.h)
+#if !defined(SCNERF_SIMT_EMU_BUILD)
+    // the pair shape runs two waves per SIMD on half of the file each: the gathering instantiation needs 238 registers, 240
+    // after allocation granularity, which would leave a guest 16 per wave, 32 per SIMD -- it declares its whole half
+    else if constexpr (LIVE) asm volatile("" ::: "v255");
+#endif
     if (blockIdx.y == 1) { a.A = a.A_y1; a.part_w = a.part_w_y1; a.part_b = a.part_b_y1; a.a = a.a_y1; }
     constexpr int TA = WA / 64, TB = WB / 64;             // accumulator tiles per wave
     constexpr int PA = WA / 64, PB = WB / 64;             // 16-byte pieces per thread and slab
@@ -173,6 +183,22 @@ __global__ __launch_bounds__(kThreads, (WA == 256 && WB == 64 && WB2 == 0) ? 2 :
     const int rd_b = rd_row * kRowEl + 2 * kPlane + rd_col;
 
     f32x4 raw[kSets][PA + PB + P2];
+    // LIVE: the original indices of the lane's two in-slab samples (ml, ml + 8) of the slab a set loads next, fetched
+    // right behind the operand loads of the slab four earlier -- the cut waits for those anyway, so no wait is added
+    int src_of[kSets][2];
+    auto load_idx = [&](auto set_tag, int s) {
+        constexpr int SET = decltype(set_tag)::value;
+        if constexpr (LIVE) {
+            s = min(s, n_slab - 1);
+            const int* li = a.live_idx + p_begin + (long)s * 16 + ml;
+            src_of[SET][0] = li[0];
+            src_of[SET][1] = li[8];
+        }
+    };
+    // piece with in-slab sample m (= ml or ml + 8, + m0) of a dense operand: tile-native of width W / row-major [P][W]
+    auto tiled_src = [&](const float* base, int W, long src, int fg) {
+        return reinterpret_cast<const f32x4*>(base + (src >> 5) * (32L * W) + ((fg >> 1) * 64 + 32 * (fg & 1) + (int)(src & 31)) * 4);
+    };
     auto load_slab = [&](auto set_tag, int s) {
         constexpr int SET = decltype(set_tag)::value;
         s = min(s, n_slab - 1);
@@ -186,7 +212,13 @@ __global__ __launch_bounds__(kThreads, (WA == 256 && WB == 64 && WB2 == 0) ? 2 :
 #pragma unroll
         for (int q = 0; q < PB; ++q) {
             const int fg = piece_fg(NPB{}, q), m = piece_m(NPB{}, q) + m0;
-            if constexpr (B_ROWMAJOR) {
+            if constexpr (LIVE) {
+                const long src = ((m - m0 - ml) >> 3) ? src_of[SET][1] : src_of[SET][0];
+                if constexpr (B_ROWMAJOR)
+                    raw[SET][PA + q] = p0 + m < a.P ? load_stream(reinterpret_cast<const f32x4*>(a.B + src * WB + 4 * fg)) : f32x4{0.f, 0.f, 0.f, 0.f};
+                else
+                    raw[SET][PA + q] = load_stream(tiled_src(a.B, WB, src, fg));
+            } else if constexpr (B_ROWMAJOR) {
                 const long p = p0 + m;
                 raw[SET][PA + q] = p < a.P ? load_stream(reinterpret_cast<const f32x4*>(a.B + p * WB + 4 * fg)) : f32x4{0.f, 0.f, 0.f, 0.f};
             } else {
@@ -197,7 +229,8 @@ __global__ __launch_bounds__(kThreads, (WA == 256 && WB == 64 && WB2 == 0) ? 2 :
             // waves 0, 1: 4-column group c of in-slab sample ml + 8 wave
             if (wave < 2) {
                 const long p = p0 + m0 + ml + 8 * wave;
-                raw[SET][PA + PB] = p < a.P ? load_stream(reinterpret_cast<const f32x4*>(a.B2 + p * WB2 + 4 * c)) : f32x4{0.f, 0.f, 0.f, 0.f};
+                const long row = LIVE ? (long)(wave ? src_of[SET][1] : src_of[SET][0]) : p;
+                raw[SET][PA + PB] = p < a.P ? load_stream(reinterpret_cast<const f32x4*>(a.B2 + row * WB2 + 4 * c)) : f32x4{0.f, 0.f, 0.f, 0.f};
             }
         }
     };
@@ -259,6 +292,7 @@ __global__ __launch_bounds__(kThreads, (WA == 256 && WB == 64 && WB2 == 0) ? 2 :
         if (s + 1 < n_slab) {
             cut_slab(next_set_tag, nxt);
             load_slab(next_set_tag, s + 5);
+            load_idx(next_set_tag, s + 9);
         }
         // product-major: the three products of one accumulator tile are TA TB MFMAs apart (back to back they would wait
         // out each other's latency: 64 cycles per dependent 32-cycle MFMA)
@@ -299,12 +333,21 @@ __global__ __launch_bounds__(kThreads, (WA == 256 && WB == 64 && WB2 == 0) ? 2 :
     using S2 = std::integral_constant<int, 2>;
     using S3 = std::integral_constant<int, 3>;
     // slab k waits in set k mod 4; slab s is cut into image s mod kImages during iteration s - 1 and read during iteration s
+    load_idx(S0{}, 0);
+    load_idx(S1{}, 1);
+    load_idx(S2{}, 2);
+    load_idx(S3{}, 3);
     load_slab(S0{}, 0);
     load_slab(S1{}, 1);
     load_slab(S2{}, 2);
     load_slab(S3{}, 3);
+    load_idx(S0{}, 4);
     cut_slab(S0{}, 0);
     load_slab(S0{}, 4);
+    load_idx(S1{}, 5);
+    load_idx(S2{}, 6);
+    load_idx(S3{}, 7);
+    load_idx(S0{}, 8);
     block_sync();
     int cur = 0, nxt = 1;
     auto step = [&](auto next_set_tag, int s) {

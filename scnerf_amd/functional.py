@@ -107,6 +107,9 @@ class RenderRaysFunction(torch.autograd.Function):
         ctx.n_params_c = len(net_c.ordered_parameters())
         ctx.coarse = (z_c, pts_c, raw_c, _c(noise_c), save_c, mx_c)
         ctx.lean = lean
+        # the backward on the live samples alone (ops.live_samples): decided here, per pass, from the arithmetic and the
+        # pass's size -- never from whether the rays need a gradient
+        ctx.live = {"coarse": ops.live_decision(n * sc, mx_c), "fine": False}
         # (the lean weight-gradient group reads three parameters of the pass's network: a snapshot, as the packed weights
         #  are -- an in-place update between forward and backward must not reach the backward)
         ctx.flat_c = flat_c.detach().clone() if lean else None
@@ -149,6 +152,7 @@ class RenderRaysFunction(torch.autograd.Function):
             rgb_f, disp_f, acc_f, _, depth_f = ops.composite_fwd(raw_f, z_f, rays, _c(noise_f), cfg.white_bkgd,
                                                                  want_weights=False)
         ctx.fine = (z_f, pts_f, raw_f, _c(noise_f), save_f, mx_f)
+        ctx.live["fine"] = ops.live_decision(n * tot, mx_f)
         ctx.flat_f = (ctx.flat_c if fine_net is net_c else flat_f.detach().clone()) if lean else None
         ctx.pl_f = pl_f
         ctx.wb_f = (ctx.wb_c if fine_net is net_c else ops.pack_weights(flat_f, "bwd")) if train else None
@@ -176,26 +180,68 @@ class RenderRaysFunction(torch.autograd.Function):
         return rgb, disp, acc, depth, raw, z_std, z_vals, z_samples
 
     @staticmethod
-    def _stage_dgrad(stage, rays, spr, wbk, white_bkgd, g_rgb, g_disp, g_acc, g_depth, g_raw, d_rays, accumulate,
-                     planes=None, guard=None, lean=False, flat_params=None):
-        """Data gradients of one stage (compositing, network, rays); -> what its weight gradients need.
-        d_rays None: the rays need no gradient -- neither the network's input gradient nor the ray reduction runs.
-        lean / flat_params: the stage's forward ran lean (ops.lean_workspace) on the network with these parameters."""
-        z, pts, raw, noise, save, maxima = stage
-        want = d_rays is not None
+    def _stage_composite_bwd(stage, rays, white_bkgd, g_rgb, g_disp, g_acc, g_depth, g_raw, want, live):
+        """The compositing's gradient of one stage -- it depends on the incoming gradients alone -- and, on the live route
+        (ops.live_samples), the compaction of its samples.  Nothing waits here.  -> (d_raw, d_rd, compaction or None)"""
+        z, _, raw, noise, _, _ = stage
         d_raw, d_rd = ops.composite_bwd(raw, z, rays, noise, white_bkgd, _c(g_rgb), _c(g_disp), _c(g_acc),
                                         _c(g_depth), _c(g_raw), want_d_rays_d=want)
-        grads, d_pts, d_views = ops.mlp_bwd(d_raw, pts, rays[:, 8:11], spr, wbk, save, planes=planes, maxima=maxima,
-                                            input_grad=want, guard=guard, lean=lean)
+        return d_raw, d_rd, ops.live_compact(d_raw) if live else None
+
+    @staticmethod
+    def _stage_dgrad(stage, first, rays, spr, wbk, d_rays, accumulate, planes=None, guard=None, lean=False, flat_params=None,
+                     guard_fwd=None):
+        """Data gradients of one stage (network, rays) behind _stage_composite_bwd (`first`); -> what its weight
+        gradients need, None when no sample is live.
+        d_rays None: the rays need no gradient -- neither the network's input gradient nor the ray reduction runs.
+        lean / flat_params: the stage's forward ran lean (ops.lean_workspace) on the network with these parameters.
+        With a compaction: the unchanged kernel on the live samples; its input gradient goes back to sample order, zero
+        rows for the dead samples, and the dense ray reduction runs.  Under the scale guard (guard_fwd / guard: the
+        pass's forward and data-gradient records) a pass whose forward tripped, or whose compact batch trips, takes the
+        dense route: the exact-fp32 rerun of a tripped block reads the dense workspace."""
+        z, pts, raw, noise, save, maxima = stage
+        d_raw, d_rd, L = first
+        want = d_rays is not None
+        P = z.shape[0] * spr
+        if L is not None and L.n > 0 and ops.live_guard_tripped(guard_fwd):
+            L = None
+        if L is not None and L.n > ops.LIVE_MAX_SHARE * P:
+            L = None               # nearly every sample is live: the compaction would cost more than it saves
+        if L is not None and L.n > 0:
+            masks, pts_l, vd_l = ops.live_gather(L, save, pts, rays[:, 8:11], spr)
+            maxima_l = ops.live_maxima(L, maxima)
+            guard_l = ops.live_guard_record(guard, L.n) if guard is not None else None
+            grads, d_pts, d_views = ops.mlp_bwd_live(L, masks, pts_l, vd_l, wbk, planes, maxima_l, input_grad=want, lean=lean,
+                                                     guard=guard_l)
+            if guard_l is not None and guard_l.rerun and ops.live_guard_tripped(guard_l):
+                L = None
+            else:
+                if guard_l is not None:
+                    ops.live_guard_keep(guard_l)
+                maxima = maxima_l
+                if want:
+                    d_pts, d_views = ops.live_scatter_rows(L, d_pts), ops.live_scatter_rows(L, d_views)
+        if L is None:
+            grads, d_pts, d_views = ops.mlp_bwd(d_raw, pts, rays[:, 8:11], spr, wbk, save, planes=planes, maxima=maxima,
+                                                input_grad=want, guard=guard, lean=lean)
+        elif L.n == 0:
+            grads = maxima = None
+            d_pts, d_views = (torch.zeros((P, 3), dtype=torch.float32, device=rays.device) for _ in range(2)) if want else (None, None)
         if want:
             ops.ray_reduce(d_pts, d_views, z, d_rd, d_rays, accumulate)
-        return save, grads, d_raw, z.shape[0] * spr, maxima, lean, flat_params
+        return save, grads, d_raw, P, maxima, lean, flat_params, L
 
     @staticmethod
     def _stage_wgrad(pending, into=None):
         """`into`: the network's attached flat .grad buffer -- the weight gradients are ADDED to it and
         None is returned (nothing for autograd to accumulate); otherwise a fresh flat gradient."""
-        save, grads, d_raw, P, maxima, lean, flat_params = pending
+        save, grads, d_raw, P, maxima, lean, flat_params, L = pending
+        if L is not None:
+            if L.n == 0:       # no live sample: the gradient is zero
+                return None if into is not None else torch.zeros(ML.N_PARAMS, dtype=torch.float32, device=d_raw.device)
+            out = ops.nerf_wgrad_live(L, save, grads, d_raw, maxima, flat_grad=into, accumulate=into is not None, lean=lean,
+                                      flat_params=flat_params)
+            return None if into is not None else out
         if into is not None:
             ops.nerf_wgrad(save, grads, d_raw, P, flat_grad=into, accumulate=True, maxima=maxima, lean=lean,
                            flat_params=flat_params)
@@ -221,21 +267,33 @@ class RenderRaysFunction(torch.autograd.Function):
         # Both stages' data gradients first, then both stages' weight gradients: the 256 x 256 weight-gradient
         # GEMMs run on the bf16 matrix pipe at a lower shader clock, and the kernel that follows them inherits
         # that clock for ~0.3 ms -- adjacent, the two passes cost one such recovery per step instead of two.
-        pend_f = pend_c = None
+        # The live route (ops.live_samples; decided in forward, per pass): the compositing gradients of both stages first
+        # -- they depend on the incoming gradients alone --, the compaction of both, ONE host read of both counts, then
+        # per stage the data gradients on the live samples.
+        pend_f = pend_c = first_f = first_c = None
+        want = d_rays is not None
         if sf > 0:
             if any(g is not None for g in (g_rgb, g_disp, g_acc, g_depth, g_raw)):
-                pend_f = RenderRaysFunction._stage_dgrad(ctx.fine, rays, sc + sf, ctx.wb_f, cfg.white_bkgd,
-                                                         g_rgb, g_disp, g_acc, g_depth, g_raw, d_rays, wrote,
-                                                         planes=ctx.pl_f, guard=ctx.guards.get("fine_bwd"), lean=ctx.lean,
-                                                         flat_params=ctx.flat_f)
-                wrote = True
+                first_f = RenderRaysFunction._stage_composite_bwd(ctx.fine, rays, cfg.white_bkgd, g_rgb, g_disp, g_acc, g_depth,
+                                                                  g_raw, want, ctx.live["fine"])
             coarse_g = (g_rgb0, g_disp0, g_acc0, g_depth0, None)
         else:
             coarse_g = (g_rgb, g_disp, g_acc, g_depth, g_raw)
         if any(g is not None for g in coarse_g):
-            pend_c = RenderRaysFunction._stage_dgrad(ctx.coarse, rays, sc, ctx.wb_c, cfg.white_bkgd,
-                                                     *coarse_g, d_rays, wrote, planes=ctx.pl_c, guard=ctx.guards.get("coarse_bwd"),
-                                                     lean=ctx.lean, flat_params=ctx.flat_c)
+            first_c = RenderRaysFunction._stage_composite_bwd(ctx.coarse, rays, cfg.white_bkgd, *coarse_g, want,
+                                                              ctx.live["coarse"])
+        compactions = [f[2] for f in (first_f, first_c) if f is not None and f[2] is not None]
+        if compactions:
+            ops.live_counts(*compactions)
+        if first_f is not None:
+            pend_f = RenderRaysFunction._stage_dgrad(ctx.fine, first_f, rays, sc + sf, ctx.wb_f, d_rays, wrote,
+                                                     planes=ctx.pl_f, guard=ctx.guards.get("fine_bwd"), lean=ctx.lean,
+                                                     flat_params=ctx.flat_f, guard_fwd=ctx.guards.get("fine"))
+            wrote = True
+        if first_c is not None:
+            pend_c = RenderRaysFunction._stage_dgrad(ctx.coarse, first_c, rays, sc, ctx.wb_c, d_rays, wrote, planes=ctx.pl_c,
+                                                     guard=ctx.guards.get("coarse_bwd"), lean=ctx.lean, flat_params=ctx.flat_c,
+                                                     guard_fwd=ctx.guards.get("coarse"))
         if pend_f is not None:
             fg_f = RenderRaysFunction._stage_wgrad(pend_f, into=into_f)
         if pend_c is not None:

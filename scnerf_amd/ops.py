@@ -1121,6 +1121,206 @@ def nerf_wgrad(save: Tensor, grads: Tensor, d_raw: Tensor, P: int, flat_grad: Op
     return flat_grad
 
 
+# ---- the backward pass on the live samples (csrc/live_compact.hip) ----------------------------------------------------
+# A sample whose noisy density is not positive has alpha = 0, so its d_raw row is all +-0 and it adds exact zeros to every
+# gradient of the network.  With the switch on, the render step's backward compacts the other samples (ascending: the
+# result is a function of the inputs alone), runs the unchanged data-gradient kernel on that batch and the weight-gradient
+# GEMMs on its dZ with X gathered from the dense workspace.  ONE host read per backward: the two counts size the launches.
+LIVE_MIN_SAMPLES = 131072       # below this a pass stays dense (the break-even against the host read)
+LIVE_MAX_SAMPLES = (1 << 22) - 128      # the gather offsets of a 256-wide section are 32 bits
+# A pass with a larger live share than this stays dense: the route costs about 0.47 ms of the headline step (the bound of
+# 1.74 ms against the 1.27 ms kept, profiles/r10_live_samples.txt) where the two dense calls take 7.1 ms, so it pays from
+# about 7 % of dead samples on.  The count is on the host by then and depends on d_raw alone.
+LIVE_MAX_SHARE = 0.9
+_LIVE_SAMPLES = _Switch((False, True), "SCNERF_LIVE_SAMPLES", parse=lambda preset: preset not in ("", "0"))
+_LIVE_MIN = [LIVE_MIN_SAMPLES]
+
+
+def live_samples(on: Optional[bool] = None, min_samples: Optional[int] = None) -> bool:
+    """Whether the render step's backward runs on the live samples alone (default on; SCNERF_LIVE_SAMPLES=0 presets it
+    off).  `min_samples`: the smallest pass that compacts (LIVE_MIN_SAMPLES; tests force it down)."""
+    if on is not None:
+        _LIVE_SAMPLES.value = bool(on)
+    if min_samples is not None:
+        _LIVE_MIN[0] = int(min_samples)
+    return _LIVE_SAMPLES.value
+
+
+def live_decision(P: int, maxima) -> bool:
+    """Whether a pass of P samples compacts -- the one copy of the rule: the switch, the resident arithmetic with its chunk
+    maxima, the half weight-gradient arithmetic, LIVE_MIN_SAMPLES <= P <= LIVE_MAX_SAMPLES.  Never a question of whether the
+    rays need a gradient: both kinds of step take the same route at the same P.  The scale guard does not enter either: a
+    step whose passes trip nothing must be the guard-off step bit for bit (tests/test_gpu_resident_guard.py), so a guarded
+    pass compacts too and goes back to the dense route only where the guard trips (live_guard_tripped)."""
+    return bool(_LIVE_SAMPLES.value and maxima is not None and wgrad_arithmetic() == "half"
+                and _LIVE_MIN[0] <= P <= LIVE_MAX_SAMPLES)
+
+
+def live_guard_record(guard: GuardRecord, n: int) -> GuardRecord:
+    """the data-gradient record of a pass for its compact batch of n samples: block flags of the compact batch (the pass's
+    own are indexed by dense blocks) and an `any` word and a report of its own, all zero -- where the compact batch trips,
+    the pass goes back to the dense route with its own record, which this launch must not have touched"""
+    nb = (int(n) + 127) // 128
+    rep = guard.report.numel() if guard.report is not None else 0
+    buf = torch.zeros(max(nb, 1) + 1 + rep, dtype=torch.float32, device=guard.any.device)
+    ints = buf.view(torch.int32)
+    return GuardRecord(guard.name, nb, ints[:max(nb, 1)], ints[max(nb, 1):max(nb, 1) + 1], buf[max(nb, 1) + 1:] if rep else None,
+                       guard.mode)
+
+
+def live_guard_keep(guard: GuardRecord):
+    """the compact batch tripped nothing: its record is the pass's latest (resident_margins)"""
+    _GUARD_LAST[guard.name] = guard
+
+
+def live_guard_tripped(guard: Optional[GuardRecord]) -> bool:
+    """Whether a guarded launch tripped (reads one device word: the guard modes pay a host wait the default does not).
+    The exact-fp32 rerun of a tripped block reads the DENSE workspace, so a pass with a tripped block -- in its forward, or
+    in the data gradients of its compact batch -- takes the dense route with the pass's own records."""
+    return guard is not None and int(guard.any.item()) != 0
+
+
+class LiveSamples:
+    """The compaction of one pass: idx int32 [padded P] (the live samples ascending, then zeros up to the padded count),
+    xoff uint32 in the 256 x 256 weight-gradient kernel's load order, d_raw [P, 4] (the live rows first), the count on the
+    device and in a pinned word; `n` once live_counts has read it."""
+    __slots__ = ("P", "idx", "xoff", "d_raw", "count", "host", "n")
+
+
+def live_compact(d_raw: Tensor) -> LiveSamples:
+    """d_raw [.., 4] -> the compaction of its samples (two launches; nothing waits here: live_counts does)."""
+    _f(d_raw, "d_raw")
+    lib = _capi.load()
+    L = LiveSamples()
+    L.P = d_raw.numel() // 4
+    dev = d_raw.device
+    Pp = ML.padded_samples(L.P)
+    both = torch.empty((2, Pp), dtype=torch.int32, device=dev)
+    L.idx, L.xoff = both[0], both[1]
+    L.d_raw = torch.empty((L.P, 4), dtype=torch.float32, device=dev)
+    L.count = torch.empty(1, dtype=torch.int32, device=dev)
+    L.host = torch.empty(1, dtype=torch.int32, device="cpu", pin_memory=d_raw.is_cuda)
+    L.n = None
+    ws = torch.empty(int(lib.scnerf_live_compact_workspace_ints(L.P)), dtype=torch.int32, device=dev)
+    st = lib.scnerf_live_compact(_p(d_raw), L.P, _p(ws), _p(L.idx), _p(L.xoff), _p(L.d_raw), _p(L.count), _p(L.host), _stream())
+    _capi.check(st, "scnerf_live_compact")
+    return L
+
+
+def live_counts(*batches: LiveSamples):
+    """THE host wait of a backward: one event behind the last compaction, then the pinned words of all of them."""
+    if batches and batches[0].d_raw.is_cuda:
+        ev = torch.cuda.Event()
+        ev.record()
+        ev.synchronize()
+    for L in batches:
+        L.n = int(L.host[0])
+    return [L.n for L in batches]
+
+
+def live_gather(L: LiveSamples, save: Tensor, pts: Tensor, viewdirs: Tensor, samples_per_ray: int, pd: int = 3):
+    """-> (masks int32, pts [n, pd], viewdirs [n, 3]) of the compact batch: what the data-gradient kernel reads"""
+    vptr, vstride = _vd(viewdirs)
+    lay = ML.layout(pd)
+    Pp, Pl = ML.padded_samples(L.P), ML.padded_samples(L.n)
+    if save.numel() < lay.save_floats(L.P):
+        raise ValueError("activation workspace too small")
+    masks = save[lay.save_floats_per_sample * Pp:]
+    dev = pts.device
+    masks_l = torch.empty(ML.MASK_WORDS_PER_SAMPLE * Pl, dtype=torch.int32, device=dev)
+    pts_l = torch.empty((L.n, pd), dtype=torch.float32, device=dev)
+    vd_l = torch.empty((L.n, 3), dtype=torch.float32, device=dev)
+    st = _capi.load().scnerf_live_gather(_p(L.idx), L.n, L.P, _p(masks), _p(pts), pd, vptr, vstride, int(samples_per_ray),
+                                         _p(masks_l), _p(pts_l), _p(vd_l), _stream())
+    _capi.check(st, "scnerf_live_gather")
+    return masks_l, pts_l, vd_l
+
+
+def live_maxima(L: LiveSamples, maxima: ChunkMaxima) -> ChunkMaxima:
+    """the chunk maxima of the compact batch: x remapped from the forward's (an upper bound per compact chunk), z left
+    to the data-gradient kernel"""
+    out = ChunkMaxima(L.n, maxima.x.device)
+    st = _capi.load().scnerf_live_remap_maxima(_p(L.idx), L.n, _p(maxima.x), maxima.chunks, maxima.chunk_samples, _p(out.x),
+                                               out.chunks, out.chunk_samples, 8, _stream())
+    _capi.check(st, "scnerf_live_remap_maxima")
+    return out
+
+
+def mlp_bwd_live(L: LiveSamples, masks: Tensor, pts: Tensor, viewdirs: Tensor, wpacked_bwd: Tensor, rw: ResidentWeights,
+                 maxima: ChunkMaxima, input_grad: bool = True, lean: bool = False, guard: Optional[GuardRecord] = None):
+    """mlp_bwd_resident on the compact batch of live_gather (one view direction per sample, the masks by their own
+    pointer): -> (grads workspace of L.n samples, d_pts [n, pd], d_views [n, 3]) in compact order.  `guard`: a record of
+    live_guard_record; "strict" raises on a trip here, the other modes leave the trip to the caller (live_guard_tripped,
+    live_guard_keep)."""
+    pd = rw.pd
+    n, dev = L.n, pts.device
+    _f(pts, "pts"), _f(viewdirs, "viewdirs"), _f(wpacked_bwd, "wpacked_bwd")
+    if pts.numel() != n * pd or viewdirs.numel() != n * 3 or masks.numel() != ML.MASK_WORDS_PER_SAMPLE * ML.padded_samples(n):
+        raise ValueError("not the compact batch of this compaction")
+    if wpacked_bwd.numel() != ML.layout(pd).bwd_total:
+        raise ValueError("wpacked_bwd has the wrong size")
+    grads = torch.empty(ML.grad_floats(n), dtype=torch.float32, device=dev)
+    d_pts = torch.empty((n, pd), dtype=torch.float32, device=dev) if input_grad else None
+    d_views = torch.empty((n, 3), dtype=torch.float32, device=dev) if input_grad else None
+    with PROFILE.region("mlp_bwd_h3_kernel%s/P=%d live" % ("" if pd == 3 else "/pd4", n), 2 * _MAC_PER_SAMPLE[pd] * n):
+        maxima.scales = rw.scales
+        st = _capi.load().scnerf_mlp_bwd_h3_masks(
+            pd, _p(L.d_raw), _p(pts), _p(viewdirs), 3, 1, _p(wpacked_bwd), _p(rw.bwd), _p(rw.scales), _p(masks), _p(grads),
+            _p(d_pts), _p(d_views), n, _p(maxima.z), maxima.chunks, maxima.chunk_samples, *_guard_args(guard), int(lean),
+            _stream())
+    _capi.check(st, "scnerf_mlp_bwd_h3_masks")
+    if guard is not None and guard.mode == "strict":
+        _GUARD_LAST[guard.name] = guard
+        guard.raise_if_tripped()
+    return grads, d_pts, d_views
+
+
+def live_scatter_rows(L: LiveSamples, rows: Tensor) -> Tensor:
+    """rows [n, w] of the compact batch -> [P, w] in sample order, zero rows for the dead samples"""
+    _f(rows, "rows")
+    w = rows.shape[1]
+    out = torch.empty((L.P, w), dtype=torch.float32, device=rows.device)
+    st = _capi.load().scnerf_live_scatter_rows(_p(rows), _p(L.idx), _p(out), L.n, w, L.P, _stream())
+    _capi.check(st, "scnerf_live_scatter_rows")
+    return out
+
+
+def nerf_wgrad_live(L: LiveSamples, save: Tensor, grads: Tensor, d_raw: Tensor, maxima: ChunkMaxima,
+                    flat_grad: Optional[Tensor] = None, pd: int = 3, accumulate: bool = False, lean: bool = False,
+                    flat_params: Optional[Tensor] = None) -> Tensor:
+    """nerf_wgrad over the live samples: `grads` and `maxima` of the compact batch (mlp_bwd_live, live_maxima), `save` and
+    `d_raw` the dense ones of the pass.  alpha_linear and rgb_linear are the dense group's, bit for bit."""
+    lib = _capi.load()
+    chunks_src, chunks = wgrad_chunks(L.P), wgrad_chunks(L.n)
+    key = (chunks_src, str(save.device))
+    if key not in _wgrad_ws:
+        _wgrad_ws[key] = torch.empty(lib.scnerf_nerf_wgrad_workspace_floats(chunks_src), dtype=torch.float32, device=save.device)
+    n_params = ML.layout(pd).n_params
+    if flat_grad is None:
+        flat_grad = torch.empty(n_params, dtype=torch.float32, device=save.device)
+    elif flat_grad.numel() != n_params or flat_grad.dtype != torch.float32 or not flat_grad.is_contiguous():
+        raise ValueError("flat_grad must be a contiguous fp32 buffer of %d elements" % n_params)
+    if maxima is None or maxima.scales is None or maxima.chunks != lib.scnerf_wgrad256_chunks(chunks):
+        raise ValueError("the live group needs the chunk maxima of the compact batch")
+    if lean and (flat_params is None or flat_params.numel() != n_params):
+        raise ValueError("the lean weight-gradient group needs flat_params")
+    if wgrad_arithmetic() != "half":
+        raise RuntimeError("the weight-gradient arithmetic was switched away from \"half\" after the compaction")
+    group = "wgrad(11 GEMMs + reduces + finish, lean, live)" if lean else "wgrad(12 GEMMs + reduces, live)"
+    with PROFILE.region("%s/P=%d of %d" % (group, L.n, L.P), 2 * _MAC_PER_SAMPLE[pd] * L.n, group=True):
+        ev = (None, None)
+        if PROFILE.enabled:
+            big = 7 if lean else 8
+            inner = PROFILE.raw_pair("wgrad256_kernel<%d GEMMs, half, live>/P=%d" % (big, L.n), big * 2 * 256 * 256 * L.n)
+            ev = (inner[0].cuda_event, inner[1].cuda_event)
+        st = lib.scnerf_nerf_wgrad_h3_live(pd, _p(save), L.P, chunks_src, _p(grads), _p(d_raw), _p(L.idx), _p(L.xoff), L.n,
+                                           chunks, _p(_wgrad_ws[key]), _p(flat_grad), int(bool(accumulate)), _p(maxima.x),
+                                           _p(maxima.z), _p(maxima.scales), _p(flat_params) if lean else None, ev[0], ev[1],
+                                           _stream())
+    _capi.check(st, "scnerf_nerf_wgrad_h3_live")
+    return flat_grad
+
+
 def composite_fwd(raw: Tensor, z: Tensor, rays: Tensor, noise: Optional[Tensor], white_bkgd: bool,
                   want_weights=True):
     _f(raw, "raw"), _f(z, "z"), _f(rays, "rays")
