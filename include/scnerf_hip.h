@@ -756,6 +756,46 @@ int scnerf_nerf_wgrad_h3_live(int pt_dims, const float* save, long long n_sample
                               const float* amax_x_live, const float* amax_z_live, const float* scales, const float* flat_params,
                               void* ev_before, void* ev_after, void* stream);
 
+/* ------------------------------------------------------------------ skipping samples in empty space: the occupancy grid --- */
+
+/* The grid: one bit per cell of an R x R x R lattice over the box [lo, hi), R a multiple of 32 in [32, 1024]; cell (x, y, z)
+ * is bit c & 31 of int32 word c >> 5, c = (z R + y) R + x.  A sample with point p is DEAD only when all three
+ * t_a = (p_a - lo_a) * inv_a (an fp32 subtraction, then an fp32 multiplication, each rounded, never fused) satisfy
+ * 0 <= t_a < R and the bit of cell (floor t_x, floor t_y, floor t_z) is 0: a NaN coordinate and a point outside the box are
+ * live.  inv_a = R / (hi_a - lo_a), computed once by the caller in fp32.
+ * scnerf_occ_compact: pts [n_samples][3] -> live_idx [n_samples] (its first n_live entries: the live samples, ascending),
+ * slot_of [n_samples] (a live sample's position among them, -1 for a dead one), pts_live / vd_live [n_samples][3] (their first
+ * n_live rows: the live points and the direction of ray i / samples_per_ray, rows of vd_stride floats) and the count, to
+ * *n_live_dev and, unless NULL, to *n_live_host, page-locked host memory the device can reach.  workspace:
+ * scnerf_occ_compact_workspace_ints(n_samples) int32.  Two launches, no atomics: the outputs are a function of the inputs
+ * alone.  n_samples == 0 stores the two zeros.
+ * scnerf_occ_expand_raw: raw [n_samples][4] = raw_live row slot_of[i], zero rows where slot_of[i] is outside [0, n_live);
+ * every row is written (16-byte rows: raw and raw_live 16-byte aligned).
+ * scnerf_occ_probe_points: cells [first_cell, first_cell + n_cells) and k in {1, 2, 3} -> pts [n_cells k^3][3]; point
+ * (jz k + jy) k + jx of cell (x, y, z) is p_a = lo_a + ((float)i_a + off_{j_a}) * cell_a: an fp32 addition, an fp32
+ * multiplication, an fp32 addition, each rounded, in this order; off_j = (j + 0.5) / k and cell_a = (hi_a - lo_a) / R are the
+ * caller's fp32 numbers.
+ * scnerf_occ_accumulate: raw [n_cells k^3][4] of those points -> the bit of a cell is OR-ed with "some probe of it has
+ * !(raw[.., 3] <= sigma_min)" (a NaN density sets the cell).  A word belongs to one wave: no atomics.
+ * scnerf_occ_dilate: one round of 26-neighbourhood dilation, bits_in -> bits_out (two different buffers); a grid edge has no
+ * neighbour.
+ * SCN_EINVAL: a NULL array with a non-zero count, R not a multiple of 32 or outside [32, 1024], n_samples >= 2^31 (or more
+ * than 2^31 - 1 probe points), first_cell not a multiple of 64, a cell range outside the grid, k outside {1, 2, 3},
+ * n_live_host not page-locked. */
+long long scnerf_occ_compact_workspace_ints(long long n_samples);
+int scnerf_occ_compact(const float* pts, long long n_samples, const float* viewdirs, int vd_stride, int samples_per_ray,
+                       const int* bits, int R, float lo_x, float lo_y, float lo_z, float inv_x, float inv_y, float inv_z,
+                       int* workspace, int* live_idx, int* slot_of, float* pts_live, float* vd_live, int* n_live_dev,
+                       int* n_live_host, void* stream);
+int scnerf_occ_expand_raw(const float* raw_live, const int* slot_of, float* raw, long long n_samples, long long n_live,
+                          void* stream);
+int scnerf_occ_probe_points(long long first_cell, long long n_cells, int R, int k, float lo_x, float lo_y, float lo_z,
+                            float cell_x, float cell_y, float cell_z, float off0, float off1, float off2, float* pts,
+                            void* stream);
+int scnerf_occ_accumulate(const float* raw, float sigma_min, long long first_cell, long long n_cells, int R, int k, int* bits,
+                          void* stream);
+int scnerf_occ_dilate(const int* bits_in, int* bits_out, int R, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

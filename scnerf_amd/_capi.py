@@ -125,6 +125,17 @@ PROTOTYPES = {
     # pt_dims, save, n_src, n_chunks_src, grads_live, d_raw, live_idx, xoff, n_live, n_chunks_live, workspace, flat_grad,
     # accumulate, amax_x_live, amax_z_live, scales, flat_params, two events
     "scnerf_nerf_wgrad_h3_live": [I, P, LL, I, P, P, P, P, LL, I, P, P, I, P, P, P, P, P, P, P],
+    # the occupancy grid: pts, n, viewdirs, vd_stride, samples_per_ray, bits, R, lo xyz, inv xyz, workspace, live_idx, slot_of,
+    # pts_live, vd_live, n_live (device word, pinned host word)
+    "scnerf_occ_compact": [P, LL, P, I, I, P, I, F, F, F, F, F, F, P, P, P, P, P, P, P, P],
+    # raw_live, slot_of, raw, n, n_live
+    "scnerf_occ_expand_raw": [P, P, P, LL, LL, P],
+    # first_cell, n_cells, R, k, lo xyz, cell xyz, the k probe offsets, pts
+    "scnerf_occ_probe_points": [LL, LL, I, I, F, F, F, F, F, F, F, F, F, P, P],
+    # raw, sigma_min, first_cell, n_cells, R, k, bits
+    "scnerf_occ_accumulate": [P, F, LL, LL, I, I, P, P],
+    # bits_in, bits_out, R
+    "scnerf_occ_dilate": [P, P, I, P],
 }
 
 
@@ -136,6 +147,7 @@ SIZE_FUNCS = {"scnerf_mlp_save_floats": [I, LL], "scnerf_mlp_grad_floats": [LL],
               "scnerf_wgrad_chunk_samples": [LL, I],
               "scnerf_camera_bwd_workspace_floats": [I],
               "scnerf_live_compact_workspace_ints": [LL],
+              "scnerf_occ_compact_workspace_ints": [LL],
               "scnerf_image_metrics_workspace_floats": [I, I, I, I, I]}
 
 

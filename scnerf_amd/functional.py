@@ -92,7 +92,17 @@ class RenderRaysFunction(torch.autograd.Function):
         guards = ops.guard_records(dev, [("coarse", n * sc)] + ([("fine", n * (sc + sf))] if sf > 0 else []), fast=fast) \
             if (resident and n > 0) else {}
         gd_c = guards.get("coarse")
-        if sc == ops.COARSE_STAGE_SAMPLES and n > 0:
+        # forward-only with ops.inference_occupancy(grid): the network of both stages on the samples the grid does not call
+        # empty.  Not with density noise: zero raw plus noise would paint fog into empty space
+        grid = ops.inference_occupancy() if (not train and n > 0 and noise_c is None and noise_f is None) else None
+        if grid is not None:
+            grid.check(net_c, net_f)
+            if grid.bits.device != dev:
+                raise ValueError("the occupancy grid lives on %s, the rays on %s" % (grid.bits.device, dev))
+            z_c, pts_c = ops.coarse_sample(rays, host_linspace(sc, dev), _c(t_rand), cfg.lindisp)
+            raw_c = RenderRaysFunction._network_on_live_samples(grid, pts_c, viewdirs, sc, wf_c, pl_c, gd_c).view(n, sc, 4)
+            rgb_c, disp_c, acc_c, w_c, depth_c = ops.composite_fwd(raw_c, z_c, rays, None, cfg.white_bkgd)
+        elif sc == ops.COARSE_STAGE_SAMPLES and n > 0:
             # the whole coarse stage -- stratified depths, network, compositing -- is one launch
             z_c, pts_c, raw_c, rgb_c, disp_c, acc_c, w_c, depth_c = ops.coarse_stage_fwd(
                 rays, host_linspace(sc, dev), _c(t_rand), cfg.lindisp, wf_c, save_c, _c(noise_c), cfg.white_bkgd,
@@ -137,11 +147,15 @@ class RenderRaysFunction(torch.autograd.Function):
             # forward-only with ops.inference_skip_empty(tau): the fine stage on the rays the coarse stage found something on
             out = RenderRaysFunction._fine_stage_on_live_rays(
                 ops.inference_skip_empty(), rays, z_c, w_c, u_dev, _c(noise_f), cfg.white_bkgd, wf_f, pl_f, gd_f,
-                (rgb_c, disp_c, acc_c, depth_c), sc, sf)
+                (rgb_c, disp_c, acc_c, depth_c), sc, sf, grid=grid)
             ctx.mark_non_differentiable(*out[5:])
             return out[:5] + (rgb_c, disp_c, acc_c, depth_c) + out[5:]
         # (with the guard on, and on the one-product arithmetic, the three launches: the same numbers as the fused stage)
-        if ops.fused_fine_stage() and gd_f is None and not fast and resident and sc == ops.COARSE_STAGE_SAMPLES and sf in ops.FINE_STAGE_IMPORTANCE and n > 0:
+        if grid is not None:
+            z_f, pts_f, z_s, z_std, _, _ = ops.fine_sample(rays, z_c, w_c, u_dev)
+            raw_f = RenderRaysFunction._network_on_live_samples(grid, pts_f, viewdirs, tot, wf_f, pl_f, gd_f).view(n, tot, 4)
+            rgb_f, disp_f, acc_f, _, depth_f = ops.composite_fwd(raw_f, z_f, rays, None, cfg.white_bkgd, want_weights=False)
+        elif ops.fused_fine_stage() and gd_f is None and not fast and resident and sc == ops.COARSE_STAGE_SAMPLES and sf in ops.FINE_STAGE_IMPORTANCE and n > 0:
             # the whole fine stage -- inverse-cdf sampler, merge, network, compositing -- as one launch (opt-in: measured
             # slower than the three launches below, ops.fused_fine_stage)
             z_f, pts_f, z_s, z_std, _, _, raw_f, rgb_f, disp_f, acc_f, depth_f, _ = ops.fine_stage_fwd(
@@ -160,7 +174,17 @@ class RenderRaysFunction(torch.autograd.Function):
         return (rgb_f, disp_f, acc_f, depth_f, raw_f, rgb_c, disp_c, acc_c, depth_c, z_std, z_f, z_s)
 
     @staticmethod
-    def _fine_stage_on_live_rays(tau, rays, z_c, w_c, u, noise_f, white_bkgd, wf_f, pl_f, gd_f, coarse, sc, sf):
+    def _network_on_live_samples(grid, pts, viewdirs, samples_per_ray, wf, pl, gd):
+        """The network of one stage of a forward-only call under ops.inference_occupancy(grid): compaction of the samples
+        the grid does not call dead (one host read: the count sizes the launch), the network on that list with one view
+        direction per sample, expansion with zero rows.  -> raw [P, 4].  All samples live goes the same way; none live
+        launches no network.  The guard record stays the dense pass's: the compact list has no more blocks."""
+        _, slot_of, pts_l, vd_l, n_live = ops.occ_compact(pts, viewdirs, samples_per_ray, grid)
+        raw_l = ops.mlp_fwd(pts_l, vd_l, 1, wf, None, planes=pl, guard=gd) if n_live > 0 else None
+        return ops.occ_expand_raw(raw_l, slot_of, n_live)
+
+    @staticmethod
+    def _fine_stage_on_live_rays(tau, rays, z_c, w_c, u, noise_f, white_bkgd, wf_f, pl_f, gd_f, coarse, sc, sf, grid=None):
         """The fine stage of a forward-only call under ops.inference_skip_empty(tau): compaction of the rays with
         acc0 > tau (one host read: the count sizes the launches), the three launches on that batch, expansion.
         -> (rgb_map, disp_map, acc_map, depth_map, raw, z_std, z_vals, z_samples) for every ray.  All rays live goes the same
@@ -173,7 +197,11 @@ class RenderRaysFunction(torch.autograd.Function):
             u_l = ops.ray_rows_gather(u, live_idx, n_live) if u.dim() == 2 else u
             noise_l = ops.ray_rows_gather(noise_f, live_idx, n_live) if noise_f is not None else None
             z_f, pts_f, z_s, z_std, _, _ = ops.fine_sample(rays_l, z_l, w_l, u_l)
-            raw_f = ops.mlp_fwd(pts_f, rays_l[:, 8:11], tot, wf_f, None, planes=pl_f, guard=gd_f).view(n_live, tot, 4)
+            if grid is not None:
+                raw_f = RenderRaysFunction._network_on_live_samples(grid, pts_f, rays_l[:, 8:11], tot, wf_f, pl_f, gd_f)
+            else:
+                raw_f = ops.mlp_fwd(pts_f, rays_l[:, 8:11], tot, wf_f, None, planes=pl_f, guard=gd_f)
+            raw_f = raw_f.view(n_live, tot, 4)
             rgb_f, disp_f, acc_f, _, depth_f = ops.composite_fwd(raw_f, z_f, rays_l, noise_l, white_bkgd, want_weights=False)
             live = (rgb_f, disp_f, acc_f, depth_f, z_std, raw_f, z_f, z_s)
         rgb, disp, acc, depth, z_std, raw, z_vals, z_samples = ops.ray_expand(slot_of, n_live, live, coarse, tot, sf)

@@ -436,6 +436,135 @@ def ray_expand(slot_of: Tensor, n_live: int, live, coarse, s_tot: int, s_fine: i
     return rgb, disp, acc, depth, z_std, raw, z_vals, z_samples
 
 
+# ---- skipping samples in empty space: the occupancy grid (csrc/occupancy.hip, scnerf_amd/occupancy.py) ----------------------
+_INFERENCE_OCCUPANCY = [None]
+_OCCUPANCY_STATS = {"samples": 0, "skipped": 0}
+
+
+def inference_occupancy(grid=None):
+    """Forward-only render_rays calls skip the network on the samples an occupancy grid calls empty: an
+    occupancy.OccupancyGrid switches it on, "off" (the default) off.  A sample is DEAD only when its point -- the fp32 point
+    the sampler wrote, in the space the network sees (after the NDC warp where there is one) -- lies inside the grid's box
+    and the bit of its cell is 0; a point outside the box and a NaN coordinate are live.  The call returns, bit for bit, what it
+    would return had the network answered raw = (0, 0, 0, 0) for every dead sample, in both passes; the fine sampler sees
+    the coarse weights that result.  Per stage: the sampler as it is, the live samples' points and view directions
+    compacted in sample order (occ_compact), mlp_fwd on that list with samples_per_ray = 1 in the arithmetic and guard mode
+    in force, the result expanded with zero rows (occ_expand_raw), the unchanged compositing -- never the one-launch
+    coarse or fine stage.  Honoured by a forward-only call on the fused path with n > 0 and no density noise (zero raw plus
+    noise would paint fog into empty space); ignored by calls that track gradients, the NeRF++ node, network queries and
+    the opaque-callable path.  Composes with inference_skip_empty(tau): the coarse stage with the grid, ray compaction by
+    acc0, the fine stage with the grid on the live rays.  A grid baked from networks checks them (OccupancyStaleError when
+    the weights have changed); a grid on another device than the rays is a ValueError.
+    ONE HOST WAIT PER STAGE AND CHUNK: the number of live samples sizes the network launch, so the host waits on an event
+    behind the compaction and reads one 4-byte word from pinned memory, exactly as ray_compact does
+    (occupancy_stats() re-uses these reads).
+    Without an argument: the grid in force, None when off.  No environment preset: a grid is not a string."""
+    if grid is not None:
+        if isinstance(grid, str) and grid == "off":
+            _INFERENCE_OCCUPANCY[0] = None
+        else:
+            from .occupancy import OccupancyGrid
+            if not isinstance(grid, OccupancyGrid):
+                raise ValueError("inference_occupancy is \"off\" or an OccupancyGrid, not %r" % (grid,))
+            _INFERENCE_OCCUPANCY[0] = grid
+    return _INFERENCE_OCCUPANCY[0]
+
+
+def occupancy_stats(reset: bool = False) -> dict:
+    """{"samples": samples compacted so far, "skipped": those of them dead}: host-side sums of the counts occ_compact has
+    already read (no device access); `reset` zeroes them after the read."""
+    out = dict(_OCCUPANCY_STATS)
+    if reset:
+        _OCCUPANCY_STATS["samples"] = _OCCUPANCY_STATS["skipped"] = 0
+    return out
+
+
+def _occ_resolution(bits: Tensor, R: int) -> int:
+    _chk(bits, torch.int32, "bits")
+    R = int(R)
+    if R < 32 or R % 32 or bits.numel() != R * R * R // 32:
+        raise ValueError("an occupancy grid of resolution %d holds %d words, not %d" % (R, R * R * R // 32, bits.numel()))
+    return R
+
+
+def occ_compact(pts: Tensor, viewdirs: Tensor, samples_per_ray: int, grid):
+    """pts [P, 3] (sample i belongs to ray i // samples_per_ray), viewdirs [n, 3], grid (bits int32 [R^3 / 32], R, lo, inv)
+    -> (live_idx int32 [P], slot_of int32 [P], pts_live [n_live, 3], vd_live [n_live, 3], n_live): the samples the grid does
+    not call dead, ascending; slot_of[i] a live sample's position among them, -1 for a dead one (csrc/occupancy.hip).
+    WAITS for the launch: n_live is read from a pinned word behind an event."""
+    _f(pts, "pts")
+    R = _occ_resolution(grid.bits, grid.resolution)
+    if grid.bits.device != pts.device:
+        raise ValueError("the occupancy grid lives on %s, the samples on %s" % (grid.bits.device, pts.device))
+    P = pts.numel() // 3
+    dev = pts.device
+    vptr, vstride = _vd(viewdirs) if P > 0 else (None, 3)
+    lib = _capi.load()
+    ints = torch.empty((2, P), dtype=torch.int32, device=dev)
+    rows = torch.empty((2, P, 3), dtype=torch.float32, device=dev)
+    ws = torch.empty(int(lib.scnerf_occ_compact_workspace_ints(P)) + 1, dtype=torch.int32, device=dev)
+    # (CPU tensors: the interpreter build of the kernels under test, which runs the launch to its end)
+    host = torch.empty(1, dtype=torch.int32, device="cpu", pin_memory=pts.is_cuda)
+    st = lib.scnerf_occ_compact(_p(pts) if P else None, P, vptr, vstride, int(samples_per_ray), _p(grid.bits), R, *grid.lo,
+                                *grid.inv, _p(ws[1:]), _p(ints[0]) if P else None, _p(ints[1]) if P else None,
+                                _p(rows[0]) if P else None, _p(rows[1]) if P else None, _p(ws[:1]), _p(host), _stream())
+    _capi.check(st, "scnerf_occ_compact")
+    if pts.is_cuda:
+        ev = torch.cuda.Event()
+        ev.record()
+        ev.synchronize()
+    n_live = int(host[0])
+    _OCCUPANCY_STATS["samples"] += P
+    _OCCUPANCY_STATS["skipped"] += P - n_live
+    return ints[0], ints[1], rows[0, :n_live], rows[1, :n_live], n_live
+
+
+def occ_expand_raw(raw_live: Optional[Tensor], slot_of: Tensor, n_live: int) -> Tensor:
+    """raw_live [n_live, 4] (None when there is none), slot_of [P] -> raw [P, 4]: row slot_of[i] of raw_live, a zero row for
+    a dead sample (one launch, every row written, no memset)."""
+    _chk(slot_of, torch.int32, "slot_of")
+    P = slot_of.numel()
+    n_live = int(n_live)
+    if n_live and (raw_live is None or _f(raw_live, "raw_live").numel() != 4 * n_live):
+        raise ValueError("occ_expand_raw: %d live samples without their [n_live, 4] outputs" % n_live)
+    raw = torch.empty((P, 4), dtype=torch.float32, device=slot_of.device)
+    st = _capi.load().scnerf_occ_expand_raw(_p(raw_live) if n_live else None, _p(slot_of) if P else None, _p(raw) if P else None,
+                                            P, n_live, _stream())
+    _capi.check(st, "scnerf_occ_expand_raw")
+    return raw
+
+
+def occ_probe_points(first_cell: int, n_cells: int, R: int, k: int, lo, cell, device) -> Tensor:
+    """The k^3 lattice points of cells [first_cell, first_cell + n_cells) of an R^3 grid -> pts [n_cells k^3, 3]; lo and
+    cell = (hi - lo) / R: three fp32 numbers each.  p = lo + (i + (j + 0.5) / k) * cell, rounded after every operation."""
+    k = int(k)
+    if k not in (1, 2, 3):
+        raise ValueError("probes is 1, 2 or 3")
+    offs = [float(np.float32(np.float32(j + 0.5) / np.float32(k))) if j < k else 0.0 for j in range(3)]
+    pts = torch.empty((int(n_cells) * k ** 3, 3), dtype=torch.float32, device=device)
+    st = _capi.load().scnerf_occ_probe_points(int(first_cell), int(n_cells), int(R), k, *lo, *cell, *offs, _p(pts), _stream())
+    _capi.check(st, "scnerf_occ_probe_points")
+    return pts
+
+
+def occ_accumulate(raw: Tensor, sigma_min: float, first_cell: int, n_cells: int, R: int, k: int, bits: Tensor) -> None:
+    """raw [n_cells k^3, 4] of occ_probe_points' points: bits |= "a probe of the cell has !(sigma <= sigma_min)" (a NaN
+    density sets the cell), in place."""
+    R = _occ_resolution(bits, R)
+    if _f(raw, "raw").numel() != 4 * int(n_cells) * int(k) ** 3:
+        raise ValueError("occ_accumulate: raw does not hold four floats per probe point")
+    st = _capi.load().scnerf_occ_accumulate(_p(raw), float(sigma_min), int(first_cell), int(n_cells), R, int(k), _p(bits), _stream())
+    _capi.check(st, "scnerf_occ_accumulate")
+
+
+def occ_dilate(bits: Tensor, R: int) -> Tensor:
+    """one round of 26-neighbourhood dilation of an R^3 grid's words -> new words"""
+    R = _occ_resolution(bits, R)
+    out = torch.empty_like(bits)
+    _capi.check(_capi.load().scnerf_occ_dilate(_p(bits), _p(out), R, _stream()), "scnerf_occ_dilate")
+    return out
+
+
 RESIDENT_GUARDS = ("off", "fallback", "report", "strict")
 # Off by default: on the headline step the fallback mode costs 1.4 - 1.5 % (medians of alternating runs in both orders,
 # profiles/r07_resident_guard.txt) -- over the half per cent a default may cost.
