@@ -796,6 +796,37 @@ int scnerf_occ_accumulate(const float* raw, float sigma_min, long long first_cel
                           void* stream);
 int scnerf_occ_dilate(const int* bits_in, int* bits_out, int R, void* stream);
 
+/* --------------------------------------------------------------- stopping rays once they are opaque: the depth segments --- */
+
+/* A stage of samples_per_ray = S samples per ray runs front to back in K segments; segment k holds the sample indices
+ * [first, first + len) of every ray, first = (k S) / K, len = ((k + 1) S) / K - first (the caller's numbers).  Element e in
+ * [0, n len) of a segment is sample first + e % len of ray e / len, dense sample i = (e / len) S + first + e % len.
+ * scnerf_seg_compact: the elements that run -- alive[ray] != 0 (alive NULL: every ray) and, with bits != NULL, the
+ * occupancy grid's cell test of pts row i (scnerf_occ_compact's) -> live_idx [n len] (its first n_live entries: the dense
+ * indices i, ascending), slot_of [n len] (by element: the position among them, -1 for one that does not run), pts_live /
+ * vd_live [n len][3] and two counts, the live samples and the rays with alive != 0, to counts_dev [2] and, unless NULL, to
+ * counts_host [2], page-locked host memory the device can reach.  workspace: scnerf_seg_compact_workspace_ints(n len)
+ * int32.  Two launches, no atomics.  n == 0 stores the zeros.
+ * scnerf_seg_expand_raw: the segment's rows of raw [n][S][4]: raw row i = raw_live row slot_of[e], a zero row where
+ * slot_of[e] is outside [0, n_live); every row of the segment is written, no row outside it (16-byte rows).
+ * scnerf_seg_transmittance: one wave per ray.  T = T_in * prod q_i over the segment's samples, q of the compositing
+ * (exp(-relu(sigma) dist) rounded as there, + 1e-10; dist 1e10 |d| for sample S - 1 alone), sigma = raw[i][3], multiplied in
+ * fp64.  k == 0: T_in = 1 for every ray, and T, alive = !(T <= eps) and stop_segment = (alive ? K : 1) are written for
+ * every ray.  k > 0: rays with alive == 0 are left as they are; the others get T, alive, and stop_segment = k + 1 where
+ * they stop.  A NaN T does not stop a ray.
+ * SCN_EINVAL: a NULL array with n > 0, a segment outside [0, S], n S >= 2^31, R as for the grid, eps outside (0, 1),
+ * k outside [0, K), counts_host not page-locked. */
+long long scnerf_seg_compact_workspace_ints(long long n_elems);
+int scnerf_seg_compact(const float* pts, long long n, int samples_per_ray, int first, int len, const int* alive,
+                       const float* viewdirs, int vd_stride, const int* bits, int R, float lo_x, float lo_y, float lo_z,
+                       float inv_x, float inv_y, float inv_z, int* workspace, int* live_idx, int* slot_of, float* pts_live,
+                       float* vd_live, int* counts_dev, int* counts_host, void* stream);
+int scnerf_seg_expand_raw(const float* raw_live, const int* slot_of, float* raw, long long n, int samples_per_ray, int first,
+                          int len, long long n_live, void* stream);
+int scnerf_seg_transmittance(const float* raw, const float* z, const float* rays, int ray_stride, long long n,
+                             int samples_per_ray, int first, int len, int k, int K, double eps, double* T, int* alive,
+                             int* stop_segment, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -136,6 +136,13 @@ PROTOTYPES = {
     "scnerf_occ_accumulate": [P, F, LL, LL, I, I, P, P],
     # bits_in, bits_out, R
     "scnerf_occ_dilate": [P, P, I, P],
+    # the depth segments of early ray termination: pts, n, samples_per_ray, first, len, alive, viewdirs, vd_stride, bits, R,
+    # lo xyz, inv xyz, workspace, live_idx, slot_of, pts_live, vd_live, the two counts (device words, pinned host words)
+    "scnerf_seg_compact": [P, LL, I, I, I, P, P, I, P, I, F, F, F, F, F, F, P, P, P, P, P, P, P, P],
+    # raw_live, slot_of, raw, n, samples_per_ray, first, len, n_live
+    "scnerf_seg_expand_raw": [P, P, P, LL, I, I, I, LL, P],
+    # raw, z, rays, ray_stride, n, samples_per_ray, first, len, k, K, eps, T, alive, stop_segment
+    "scnerf_seg_transmittance": [P, P, P, I, LL, I, I, I, I, I, D, P, P, P, P],
 }
 
 
@@ -148,6 +155,7 @@ SIZE_FUNCS = {"scnerf_mlp_save_floats": [I, LL], "scnerf_mlp_grad_floats": [LL],
               "scnerf_camera_bwd_workspace_floats": [I],
               "scnerf_live_compact_workspace_ints": [LL],
               "scnerf_occ_compact_workspace_ints": [LL],
+              "scnerf_seg_compact_workspace_ints": [LL],
               "scnerf_image_metrics_workspace_floats": [I, I, I, I, I]}
 
 

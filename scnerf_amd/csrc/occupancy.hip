@@ -32,6 +32,7 @@
 #include <cstdint>
 
 #include "launch.h"
+#include "occ_cell.h"
 #include "scn_wave.h"
 #include "scnerf_hip.h"
 
@@ -46,46 +47,12 @@ constexpr int kOccThreads = kOccWaves * kWave;
 constexpr int kTilesPerWave = 4;
 constexpr int kOccBlock = kOccThreads * kTilesPerWave;           // samples per workgroup
 
-// a - b and a * b, each rounded once (the build runs with -ffp-contract=off; on the device the intrinsics say so again)
-__device__ __forceinline__ float sub_rn(float a, float b) {
-#if defined(SCNERF_SIMT_EMU_BUILD)
-    return a - b;
-#else
-    return __fsub_rn(a, b);
-#endif
-}
-__device__ __forceinline__ float mul_rn(float a, float b) {
-#if defined(SCNERF_SIMT_EMU_BUILD)
-    return a * b;
-#else
-    return __fmul_rn(a, b);
-#endif
-}
-__device__ __forceinline__ float add_rn(float a, float b) {
-#if defined(SCNERF_SIMT_EMU_BUILD)
-    return a + b;
-#else
-    return __fadd_rn(a, b);
-#endif
-}
-
-struct Grid {
-    const unsigned* bits;        // [R^3 / 32]
-    int R;
-    float lo_x, lo_y, lo_z, inv_x, inv_y, inv_z;
-};
-
-__device__ __forceinline__ bool sample_live(const Grid& g, const float* __restrict__ pts, long i) {
-    const float fr = (float)g.R;
-    const float tx = mul_rn(sub_rn(pts[3 * i + 0], g.lo_x), g.inv_x);
-    const float ty = mul_rn(sub_rn(pts[3 * i + 1], g.lo_y), g.inv_y);
-    const float tz = mul_rn(sub_rn(pts[3 * i + 2], g.lo_z), g.inv_z);
-    const bool inside = tx >= 0.f && tx < fr && ty >= 0.f && ty < fr && tz >= 0.f && tz < fr;      // (false with a NaN)
-    if (!inside) return true;
-    // 0 <= t < R: the conversion truncates towards zero, which is floor here (-0.0 -> cell 0)
-    const long c = ((long)(int)tz * g.R + (int)ty) * g.R + (int)tx;
-    return ((g.bits[c >> 5] >> (unsigned)(c & 31)) & 1u) != 0u;
-}
+// the cell test of a sample and the once-rounded fp32 operations: occ_cell.h, shared with early_stop.hip
+using occ::add_rn;
+using occ::bad_resolution;
+using occ::Grid;
+using occ::mul_rn;
+using occ::sample_live;
 
 // sample i of wave w, tile k of workgroup b
 __device__ __forceinline__ long sample_of(long b, int w, int k, int lane) {
@@ -241,8 +208,6 @@ __global__ __launch_bounds__(256) void occ_dilate_kernel(const unsigned* __restr
     }
     out[e] = m | (m << 1) | (m >> 1) | (l >> 31) | (r << 31);
 }
-
-bool bad_resolution(int R) { return R < 32 || R > 1024 || (R & 31) != 0; }
 
 }  // namespace
 

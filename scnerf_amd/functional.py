@@ -95,12 +95,18 @@ class RenderRaysFunction(torch.autograd.Function):
         # forward-only with ops.inference_occupancy(grid): the network of both stages on the samples the grid does not call
         # empty.  Not with density noise: zero raw plus noise would paint fog into empty space
         grid = ops.inference_occupancy() if (not train and n > 0 and noise_c is None and noise_f is None) else None
+        # forward-only with ops.inference_early_stop(eps, K): the network of the call's FINAL stage front to back in K depth
+        # segments, the rays that have gone opaque left out of the later ones.  Under the same conditions as the grid
+        stop = ops.inference_early_stop() if (not train and n > 0 and noise_c is None and noise_f is None) else None
         if grid is not None:
             grid.check(net_c, net_f)
             if grid.bits.device != dev:
                 raise ValueError("the occupancy grid lives on %s, the rays on %s" % (grid.bits.device, dev))
+        if grid is not None or (stop is not None and sf == 0):
             z_c, pts_c = ops.coarse_sample(rays, host_linspace(sc, dev), _c(t_rand), cfg.lindisp)
-            raw_c = RenderRaysFunction._network_on_live_samples(grid, pts_c, viewdirs, sc, wf_c, pl_c, gd_c).view(n, sc, 4)
+            # (with a fine stage behind it the coarse stage is never cut short: its weights feed the sampler)
+            raw_c = RenderRaysFunction._stage_network(pts_c, viewdirs, sc, wf_c, pl_c, gd_c, grid,
+                                                      stop + (z_c, rays) if (stop is not None and sf == 0) else None).view(n, sc, 4)
             rgb_c, disp_c, acc_c, w_c, depth_c = ops.composite_fwd(raw_c, z_c, rays, None, cfg.white_bkgd)
         elif sc == ops.COARSE_STAGE_SAMPLES and n > 0:
             # the whole coarse stage -- stratified depths, network, compositing -- is one launch
@@ -147,13 +153,14 @@ class RenderRaysFunction(torch.autograd.Function):
             # forward-only with ops.inference_skip_empty(tau): the fine stage on the rays the coarse stage found something on
             out = RenderRaysFunction._fine_stage_on_live_rays(
                 ops.inference_skip_empty(), rays, z_c, w_c, u_dev, _c(noise_f), cfg.white_bkgd, wf_f, pl_f, gd_f,
-                (rgb_c, disp_c, acc_c, depth_c), sc, sf, grid=grid)
+                (rgb_c, disp_c, acc_c, depth_c), sc, sf, grid=grid, stop=stop)
             ctx.mark_non_differentiable(*out[5:])
             return out[:5] + (rgb_c, disp_c, acc_c, depth_c) + out[5:]
         # (with the guard on, and on the one-product arithmetic, the three launches: the same numbers as the fused stage)
-        if grid is not None:
+        if grid is not None or stop is not None:
             z_f, pts_f, z_s, z_std, _, _ = ops.fine_sample(rays, z_c, w_c, u_dev)
-            raw_f = RenderRaysFunction._network_on_live_samples(grid, pts_f, viewdirs, tot, wf_f, pl_f, gd_f).view(n, tot, 4)
+            raw_f = RenderRaysFunction._stage_network(pts_f, viewdirs, tot, wf_f, pl_f, gd_f, grid,
+                                                      stop + (z_f, rays) if stop is not None else None).view(n, tot, 4)
             rgb_f, disp_f, acc_f, _, depth_f = ops.composite_fwd(raw_f, z_f, rays, None, cfg.white_bkgd, want_weights=False)
         elif ops.fused_fine_stage() and gd_f is None and not fast and resident and sc == ops.COARSE_STAGE_SAMPLES and sf in ops.FINE_STAGE_IMPORTANCE and n > 0:
             # the whole fine stage -- inverse-cdf sampler, merge, network, compositing -- as one launch (opt-in: measured
@@ -174,21 +181,55 @@ class RenderRaysFunction(torch.autograd.Function):
         return (rgb_f, disp_f, acc_f, depth_f, raw_f, rgb_c, disp_c, acc_c, depth_c, z_std, z_f, z_s)
 
     @staticmethod
-    def _network_on_live_samples(grid, pts, viewdirs, samples_per_ray, wf, pl, gd):
-        """The network of one stage of a forward-only call under ops.inference_occupancy(grid): compaction of the samples
-        the grid does not call dead (one host read: the count sizes the launch), the network on that list with one view
-        direction per sample, expansion with zero rows.  -> raw [P, 4].  All samples live goes the same way; none live
-        launches no network.  The guard record stays the dense pass's: the compact list has no more blocks."""
-        _, slot_of, pts_l, vd_l, n_live = ops.occ_compact(pts, viewdirs, samples_per_ray, grid)
-        raw_l = ops.mlp_fwd(pts_l, vd_l, 1, wf, None, planes=pl, guard=gd) if n_live > 0 else None
-        return ops.occ_expand_raw(raw_l, slot_of, n_live)
+    def _stage_network(pts, viewdirs, samples_per_ray, wf, pl, gd, grid=None, stop=None):
+        """The network of one stage of a forward-only call -> raw [P, 4].
+        Neither switch: the dense pass.
+        `grid` (ops.inference_occupancy): compaction of the samples the grid does not call dead (one host read: the count
+        sizes the launch), the network on that list with one view direction per sample, expansion with zero rows.  All
+        samples live goes the same way; none live launches no network.  The guard record stays the dense pass's: the
+        compact list has no more blocks.
+        `stop` = (eps, K, z, rays) (ops.inference_early_stop, the call's final stage): the same three steps per depth
+        segment, front to back, on the samples whose ray is alive (and the grid calls live); behind every segment but the
+        last the rays' transmittance decides who goes on.  The first pass without a grid knows its count; every other
+        pass reads one.  Every pass takes a guard record of its own, so that none reads block flags another left behind."""
+        if stop is None:
+            if grid is None:
+                return ops.mlp_fwd(pts, viewdirs, samples_per_ray, wf, None, planes=pl, guard=gd)
+            _, slot_of, pts_l, vd_l, n_live = ops.occ_compact(pts, viewdirs, samples_per_ray, grid)
+            raw_l = ops.mlp_fwd(pts_l, vd_l, 1, wf, None, planes=pl, guard=gd) if n_live > 0 else None
+            return ops.occ_expand_raw(raw_l, slot_of, n_live)
+        eps, K, z, rays = stop
+        S = samples_per_ray
+        n = z.shape[0]
+        b = ops.segment_bounds(S, K)
+        raw = torch.empty((n * S, 4), dtype=torch.float32, device=pts.device)
+        state = ops.StopState(n, pts.device)
+        ran, n_rays = 0, n
+        for k in range(K):
+            first, length = b[k], b[k + 1] - b[k]
+            opening = k == 0
+            _, slot_of, pts_l, vd_l, n_live, n_rays = ops.seg_compact(
+                pts, viewdirs, S, first, length, None if opening else state.alive, grid, read=not (opening and grid is None))
+            raw_l = None
+            if n_live > 0:
+                name = "%s/%d" % (gd.name, k) if gd is not None else None
+                gd_k = ops.guard_records(pts.device, [(name, n_live)])[name] if gd is not None else None
+                raw_l = ops.mlp_fwd(pts_l, vd_l, 1, wf, None, planes=pl, guard=gd_k)
+            ops.seg_expand_raw(raw_l, slot_of, raw, S, first, length, n_live)
+            ran += n_live
+            if k < K - 1:
+                ops.seg_transmittance(raw, z, rays, first, length, k, K, eps, state)
+        ops.early_stop_count(n, S, ran, n_rays, state.stop_segment)
+        return raw
 
     @staticmethod
-    def _fine_stage_on_live_rays(tau, rays, z_c, w_c, u, noise_f, white_bkgd, wf_f, pl_f, gd_f, coarse, sc, sf, grid=None):
+    def _fine_stage_on_live_rays(tau, rays, z_c, w_c, u, noise_f, white_bkgd, wf_f, pl_f, gd_f, coarse, sc, sf, grid=None,
+                                 stop=None):
         """The fine stage of a forward-only call under ops.inference_skip_empty(tau): compaction of the rays with
         acc0 > tau (one host read: the count sizes the launches), the three launches on that batch, expansion.
         -> (rgb_map, disp_map, acc_map, depth_map, raw, z_std, z_vals, z_samples) for every ray.  All rays live goes the same
-        way; none live launches nothing but the expansion."""
+        way; none live launches nothing but the expansion.  `grid` / `stop` = (eps, K): the network of the live rays as
+        _stage_network runs it under ops.inference_occupancy / ops.inference_early_stop."""
         tot = sc + sf
         live_idx, slot_of, n_live = ops.ray_compact(coarse[2], tau)
         live = None
@@ -197,10 +238,8 @@ class RenderRaysFunction(torch.autograd.Function):
             u_l = ops.ray_rows_gather(u, live_idx, n_live) if u.dim() == 2 else u
             noise_l = ops.ray_rows_gather(noise_f, live_idx, n_live) if noise_f is not None else None
             z_f, pts_f, z_s, z_std, _, _ = ops.fine_sample(rays_l, z_l, w_l, u_l)
-            if grid is not None:
-                raw_f = RenderRaysFunction._network_on_live_samples(grid, pts_f, rays_l[:, 8:11], tot, wf_f, pl_f, gd_f)
-            else:
-                raw_f = ops.mlp_fwd(pts_f, rays_l[:, 8:11], tot, wf_f, None, planes=pl_f, guard=gd_f)
+            raw_f = RenderRaysFunction._stage_network(pts_f, rays_l[:, 8:11], tot, wf_f, pl_f, gd_f, grid,
+                                                      stop + (z_f, rays_l) if stop is not None else None)
             raw_f = raw_f.view(n_live, tot, 4)
             rgb_f, disp_f, acc_f, _, depth_f = ops.composite_fwd(raw_f, z_f, rays_l, noise_l, white_bkgd, want_weights=False)
             live = (rgb_f, disp_f, acc_f, depth_f, z_std, raw_f, z_f, z_s)

@@ -565,6 +565,209 @@ def occ_dilate(bits: Tensor, R: int) -> Tensor:
     return out
 
 
+# ---- stopping rays once they are opaque: early ray termination (csrc/early_stop.hip) -----------------------------------------
+EARLY_STOP_SEGMENTS = (2, 8)                   # K, inclusive
+EARLY_STOP_DEFAULT_SEGMENTS = 4
+
+
+class _EarlyStopSwitch:
+    """_FloatSwitch's sibling for a pair: (eps, K) -- eps a float in (0, 1), the double the kernels compare with, K the
+    number of depth segments in 2 .. 8 -- or off (None).  The preset comes from the environment variable `env`: "off" (or
+    empty, unset), "eps" or "eps:segments".  Anything else raises ValueError."""
+
+    def __init__(self, env, what):
+        self.what = what
+        preset = os.environ.get(env)
+        self.value = None
+        if preset not in (None, "", "off"):
+            eps, _, segments = preset.partition(":")
+            self.value = self._parse(eps, self._int(segments, env) if segments or ":" in preset else None, env)
+
+    @staticmethod
+    def _int(text, what):
+        try:
+            return int(text)
+        except ValueError:
+            raise ValueError("%s is \"off\", eps or eps:segments, not %r" % (what, text)) from None
+
+    def _parse(self, eps, segments, what):
+        try:
+            x = float(eps) if not isinstance(eps, bool) else None
+        except (TypeError, ValueError):
+            x = None
+        if x is None or not (0.0 < x < 1.0):
+            raise ValueError("%s: eps is \"off\" or a number in (0, 1), not %r" % (what, eps))
+        k = EARLY_STOP_DEFAULT_SEGMENTS if segments is None else segments
+        lo, hi = EARLY_STOP_SEGMENTS
+        if isinstance(k, bool) or not isinstance(k, int) or not (lo <= k <= hi):
+            raise ValueError("%s: segments is an integer in %d .. %d, not %r" % (what, lo, hi, segments))
+        return x, k
+
+    def __call__(self, eps=None, segments=None):
+        if eps is None:
+            if segments is not None:
+                raise ValueError("%s: segments go with an eps" % self.what)
+        elif isinstance(eps, str) and eps == "off":
+            self.value = None
+        else:
+            self.value = self._parse(eps, segments, self.what)
+        return self.value
+
+
+_INFERENCE_EARLY_STOP = _EarlyStopSwitch("SCNERF_INFER_EARLY_STOP", "inference_early_stop")
+_EARLY_STOP_STATS = {"samples": 0, "skipped": 0, "rays": 0, "stopped": 0}
+_EARLY_STOP_LAST = [None]
+
+
+def inference_early_stop(eps=None, segments=None):
+    """Forward-only render_rays calls stop a ray once it is opaque: a float eps in (0, 1) switches it on, with `segments`
+    = K in 2 .. 8 depth segments (4 when not given), "off" (the default) off.  The network of the call's FINAL stage -- the
+    fine stage, or the coarse stage when N_importance == 0; S samples per ray, K <= S -- runs front to back in K passes:
+    segment k holds the sample indices [b_k, b_k+1), b_k = (k S) // K.  After segment k the ray's transmittance T is the
+    product of q_i over i < b_k+1, q exactly the compositing's (ray::sample_terms, noise 0), multiplied in fp64; a ray
+    with T <= eps is STOPPED (a NaN T is not), and its samples in all later segments do not reach the network.  The call
+    returns, bit for bit in all twelve outputs, what it would return had the network answered raw = (0, 0, 0, 0) for every
+    skipped sample: raw carries those zero rows, the compositing is unchanged.  Colours lie in [0, 1] and the skipped weights
+    sum to at most T, so every rgb_map channel and acc_map move by at most eps (in exact arithmetic), with and without
+    white_bkgd.  With N_importance > 0 the coarse stage is never touched: its weights feed the sampler.
+    Honoured by a forward-only call on the fused path with n > 0 and no density noise; ignored by calls that track gradients,
+    the NeRF++ node, network queries and the opaque-callable path.  Composes with inference_skip_empty (ray compaction
+    first, the segments on the live rays), inference_occupancy (a sample runs only if the grid calls it live AND its ray is
+    alive), inference_arithmetic("fast") and resident_guard (one record per segment pass, "fine/0" .. "fine/K-1").
+    HOST WAITS: every pass but the first (every pass, with a grid) sizes its network launch by a count the host reads from
+    pinned memory behind an event (early_stop_stats() re-uses these reads).
+    Without an argument: (eps, K) in force, None when off.  Environment preset: SCNERF_INFER_EARLY_STOP = off | eps |
+    eps:segments."""
+    return _INFERENCE_EARLY_STOP(eps, segments)
+
+
+def early_stop_stats(reset: bool = False) -> dict:
+    """{"samples": samples of the final stages run in segments so far, "skipped": those of them that did not reach the
+    network (with an occupancy grid: for either reason), "rays": their rays, "stopped": those of them stopped before the
+    last segment}: host-side sums of the counts seg_compact has already read (no device access); `reset` zeroes them after
+    the read."""
+    out = dict(_EARLY_STOP_STATS)
+    if reset:
+        for k in _EARLY_STOP_STATS:
+            _EARLY_STOP_STATS[k] = 0
+    return out
+
+
+def early_stop_last() -> Optional[Tensor]:
+    """stop_segment int32 [n] of the latest stage run in segments (the first segment not run, K for a ray that ran them all;
+    with inference_skip_empty: of the live rays), None before the first; a device tensor, nothing waits here"""
+    return _EARLY_STOP_LAST[0]
+
+
+def segment_bounds(samples_per_ray: int, segments: int) -> list:
+    """b_0 .. b_K of the K depth segments of a stage of S samples: b_k = (k S) // K"""
+    S, K = int(samples_per_ray), int(segments)
+    if not EARLY_STOP_SEGMENTS[0] <= K <= EARLY_STOP_SEGMENTS[1] or K > S:
+        raise ValueError("%d depth segments for %d samples per ray: segments in 2 .. 8 and at most the samples" % (K, S))
+    return [(k * S) // K for k in range(K + 1)]
+
+
+def seg_compact(pts: Tensor, viewdirs: Tensor, samples_per_ray: int, first: int, length: int, alive: Optional[Tensor] = None,
+                grid=None, read: bool = True):
+    """pts [n S, 3], viewdirs [n, 3]; the samples [first, first + length) of every ray whose ray is alive (alive int32 [n],
+    None: every ray) and which `grid` (an OccupancyGrid or None) does not call dead -> (live_idx int32 [n length] -- dense
+    sample indices, ascending --, slot_of int32 [n length] by segment element, pts_live [n_live, 3], vd_live [n_live, 3],
+    n_live, alive rays) (csrc/early_stop.hip).  `read`: WAITS for the launch and reads the two counts from pinned words
+    behind an event; False -- for a pass without flags and grid, whose counts the host knows -- waits for nothing."""
+    _f(pts, "pts")
+    S, first, length = int(samples_per_ray), int(first), int(length)
+    n = pts.numel() // (3 * S)
+    if pts.numel() != 3 * S * n or not (0 <= first and 1 <= length <= S - first):
+        raise ValueError("seg_compact: samples [%d, %d) of %d per ray, %d points" % (first, first + length, S, pts.numel() // 3))
+    dev = pts.device
+    if alive is not None and _chk(alive, torch.int32, "alive").numel() != n:
+        raise ValueError("seg_compact: one alive flag per ray")
+    if not read and (alive is not None or grid is not None):
+        raise ValueError("seg_compact: only a pass without flags and grid knows its counts")
+    bits, R, box = None, 0, (0.0,) * 6
+    if grid is not None:
+        R = _occ_resolution(grid.bits, grid.resolution)
+        if grid.bits.device != dev:
+            raise ValueError("the occupancy grid lives on %s, the samples on %s" % (grid.bits.device, dev))
+        bits, box = grid.bits, tuple(grid.lo) + tuple(grid.inv)
+    E = n * length
+    vptr, vstride = _vd(viewdirs) if n > 0 else (None, 3)
+    lib = _capi.load()
+    ints = torch.empty((2, E), dtype=torch.int32, device=dev)
+    rows = torch.empty((2, E, 3), dtype=torch.float32, device=dev)
+    ws = torch.empty(int(lib.scnerf_seg_compact_workspace_ints(E)) + 2, dtype=torch.int32, device=dev)
+    # (CPU tensors: the interpreter build of the kernels under test, which runs the launch to its end)
+    host = torch.empty(2, dtype=torch.int32, device="cpu", pin_memory=pts.is_cuda) if read else None
+    st = lib.scnerf_seg_compact(_p(pts) if n else None, n, S, first, length, _p(alive), vptr, vstride, _p(bits), R, *box,
+                                _p(ws[2:]), _p(ints[0]) if E else None, _p(ints[1]) if E else None, _p(rows[0]) if E else None,
+                                _p(rows[1]) if E else None, _p(ws[:2]), _p(host), _stream())
+    _capi.check(st, "scnerf_seg_compact")
+    if read:
+        if pts.is_cuda:
+            ev = torch.cuda.Event()
+            ev.record()
+            ev.synchronize()
+        n_live, n_rays = int(host[0]), int(host[1])
+    else:
+        n_live, n_rays = E, n
+    return ints[0], ints[1], rows[0, :n_live], rows[1, :n_live], n_live, n_rays
+
+
+def seg_expand_raw(raw_live: Optional[Tensor], slot_of: Tensor, raw: Tensor, samples_per_ray: int, first: int, length: int,
+                   n_live: int) -> Tensor:
+    """raw_live [n_live, 4] (None when there is none), slot_of [n length] -> the rows [first, first + length) of every ray of
+    the dense raw [n, S, 4], in place: row slot_of[e] of raw_live, a zero row for a sample that did not run (one launch,
+    every row of the segment written, none outside it)."""
+    _chk(slot_of, torch.int32, "slot_of"), _f(raw, "raw")
+    S, first, length, n_live = int(samples_per_ray), int(first), int(length), int(n_live)
+    n = raw.numel() // (4 * S)
+    if raw.numel() != 4 * S * n or slot_of.numel() != n * length or slot_of.device != raw.device:
+        raise ValueError("seg_expand_raw: raw [n, %d, 4] and one slot per sample of the segment" % S)
+    if n_live and (raw_live is None or _f(raw_live, "raw_live").numel() != 4 * n_live):
+        raise ValueError("seg_expand_raw: %d live samples without their [n_live, 4] outputs" % n_live)
+    st = _capi.load().scnerf_seg_expand_raw(_p(raw_live) if n_live else None, _p(slot_of) if n else None, _p(raw) if n else None,
+                                            n, S, first, length, n_live, _stream())
+    _capi.check(st, "scnerf_seg_expand_raw")
+    return raw
+
+
+class StopState:
+    """What the segments of one stage carry from pass to pass: T float64 [n], alive int32 [n], stop_segment int32 [n]
+    (csrc/early_stop.hip); segment 0 writes all three, so nothing is filled here."""
+    __slots__ = ("T", "alive", "stop_segment")
+
+    def __init__(self, n: int, device):
+        self.T = torch.empty((n,), dtype=torch.float64, device=device)
+        both = torch.empty((2, n), dtype=torch.int32, device=device)
+        self.alive, self.stop_segment = both[0], both[1]
+
+
+def seg_transmittance(raw: Tensor, z: Tensor, rays: Tensor, first: int, length: int, k: int, segments: int, eps: float,
+                      state: StopState) -> None:
+    """The transmittance behind segment k = samples [first, first + length) of every ray, from the dense raw [n, S, 4], the
+    depths z [n, S] and the ray batch: state.T *= prod q (fp64), state.alive = !(T <= eps), state.stop_segment = k + 1
+    where a ray stops; k == 0 starts every ray at T = 1 and writes all three arrays, a later k leaves stopped rays as they
+    are (one launch, one wave per ray)."""
+    _f(raw, "raw"), _f(z, "z"), _f(rays, "rays")
+    n, S = z.shape
+    if raw.numel() != 4 * n * S or rays.shape[0] != n or state.T.numel() != n:
+        raise ValueError("seg_transmittance: raw [n, S, 4], z [n, S], rays [n, .] and the state of n rays")
+    st = _capi.load().scnerf_seg_transmittance(_p(raw), _p(z), _p(rays), int(rays.stride(0)), n, S, int(first), int(length),
+                                               int(k), int(segments), float(eps), _p(state.T), _p(state.alive),
+                                               _p(state.stop_segment), _stream())
+    _capi.check(st, "scnerf_seg_transmittance")
+
+
+def early_stop_count(n: int, samples_per_ray: int, ran: int, alive_last: int, stop_segment: Tensor) -> None:
+    """one stage run in segments enters early_stop_stats(): `ran` of its n S samples reached the network, `alive_last` of
+    its rays were alive in the last segment"""
+    _EARLY_STOP_STATS["samples"] += n * samples_per_ray
+    _EARLY_STOP_STATS["skipped"] += n * samples_per_ray - ran
+    _EARLY_STOP_STATS["rays"] += n
+    _EARLY_STOP_STATS["stopped"] += n - alive_last
+    _EARLY_STOP_LAST[0] = stop_segment
+
+
 RESIDENT_GUARDS = ("off", "fallback", "report", "strict")
 # Off by default: on the headline step the fallback mode costs 1.4 - 1.5 % (medians of alternating runs in both orders,
 # profiles/r07_resident_guard.txt) -- over the half per cent a default may cost.
