@@ -572,6 +572,22 @@ int scnerf_npp_composite_bwd(const float* raw_fg, const float* raw_bg, const flo
                              float* d_raw_fg, float* d_raw_bg, float* d_fg_z, float* d_fg_z_max, float* d_norm,
                              int n, int sf, int sb, void* stream);
 
+/* Forward-only NerfNet.forward with the background skipped behind an opaque foreground (ops.inference_skip_background).
+ * scnerf_npp_fg_lambda: bg_lambda [n] alone from the foreground's raw outputs -- the foreground sweep of
+ * scnerf_npp_composite_fwd on the same inputs, bit for bit its bg_lambda -- before the background network is launched.
+ * scnerf_npp_composite_fwd_skip: scnerf_npp_composite_fwd with raw_bg_live [n_live, sb, 4] holding the rows of the live
+ * rays only, slot_of [n] (scnerf_ray_compact's: a live ray's row, anything outside [0, n_live) for a skipped ray).  A
+ * skipped ray runs no background sweep: its bg_weights row is zero, bg_rgb = bg_depth = +0, rgb = fg_rgb + 0 -- what a
+ * zero raw_bg row gives.  Every element of every output is written; bg_z stays [n, sb]; raw_bg_live may be NULL when
+ * n_live == 0.  n == 0 is a no-op.  SCN_EINVAL: a NULL array, n < 0, sf < 1, sb < 1, n_live outside [0, n]. */
+int scnerf_npp_fg_lambda(const float* raw_fg, const float* fg_z, const float* fg_z_max, const float* ray_d,
+                         float* bg_lambda, int n, int sf, void* stream);
+int scnerf_npp_composite_fwd_skip(const float* raw_fg, const float* raw_bg_live, const float* fg_z,
+                                  const float* fg_z_max, const float* bg_z, const float* ray_d, const int* slot_of,
+                                  float* rgb, float* fg_weights, float* bg_weights, float* fg_rgb, float* fg_depth,
+                                  float* bg_rgb, float* bg_depth, float* bg_lambda, int n, int n_live, int sf, int sb,
+                                  void* stream);
+
 /* render_ray_from_camera (nerfplusplus/nerf_sample_ray_split.py:196-257): rays of the
  * row-major pixel indices select [n] (int64) through the CENTRES of those pixels, optional radial
  * distortion dist2 = (k0, k1): p <- (p - c)(1 + r^2 k0 + r^4 k1) + c, r = (p - c) / c per axis (:225-232);

@@ -53,6 +53,10 @@ PROTOTYPES = {
     "scnerf_npp_points_bwd": [P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, P],
     "scnerf_npp_composite_fwd": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, P],
     "scnerf_npp_composite_bwd": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, P],
+    # the background skipped behind an opaque foreground: raw_fg, fg_z, fg_z_max, ray_d, bg_lambda, n, sf
+    "scnerf_npp_fg_lambda": [P, P, P, P, P, I, I, P],
+    # composite_fwd's six inputs (raw_bg: the live rows), slot_of, the eight outputs, n, n_live, sf, sb
+    "scnerf_npp_composite_fwd_skip": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P],
     "scnerf_npp_camera_rays_fwd": [P, P, I, P, P, P, F, I, P, P, F, I, P, F, P, F, I, I, I, I, P, P, I, P],
     "scnerf_npp_camera_rays_bwd": [P, P, I, P, P, P, F, I, P, P, F, I, P, F, P, F, I, I, I, I, P, P, P, P, P, P, P,
                                    P, P, I, P],

@@ -9,6 +9,8 @@
 // One 64-lane wave owns one ray.  Arithmetic is rounded op by op (-ffp-contract=off) like the reference's
 // fp32 tensor code; the pdf normaliser uses ATen's row-sum order, running products / prefix sums are
 // carried in fp64 and rounded per element as ATen's CPU cumprod / cumsum do for float.
+#include <cstdint>
+
 #include <scn_wave.h>
 
 #include "aten_sum.h"
@@ -470,6 +472,63 @@ __global__ __launch_bounds__(256) void npp_composite_fwd_kernel(
     }
 }
 
+// ---- forward-only: the background behind an opaque foreground is not evaluated (ops.inference_skip_background) ----
+// bg_lambda alone, before the background network is launched: the foreground sweep of npp_composite_fwd_kernel, the
+// same code on the same inputs, so the value is that kernel's bit for bit (raw_bg / bg_z of `a` are not read)
+__global__ __launch_bounds__(256) void npp_fg_lambda_kernel(CompArgs a, float* __restrict__ bg_lambda) {
+    const int lane = lane_id();
+    int ray = blockIdx.x * kRaysPerBlock + wave_id();
+    const bool live = ray < a.n;
+    if (!live) ray = a.n - 1;
+    const V3 d = ld3(a.rd, ray);
+    const float norm = sqrtf(dot(d, d));
+    double f3[3], fd;
+    float lambda;
+    sweep<true>(a, ray, lane, norm, nullptr, nullptr, nullptr, false, f3, &fd, &lambda);
+    if (live && lane == 0) bg_lambda[ray] = lambda;
+}
+
+// npp_composite_fwd_kernel with a.raw_bg [n_live, sb, 4] holding the rows of the live rays only: ray i with
+// s = slot_of[i] in [0, n_live) sweeps row s; any other ray (skipped) runs no background sweep and takes what a zero
+// raw_bg row gives -- zero weights, bg_rgb = bg_depth = +0, rgb = fg_rgb + 0.  Every element of every output is written.
+__global__ __launch_bounds__(256) void npp_composite_fwd_skip_kernel(
+    CompArgs a, const int* __restrict__ slot_of, int n_live, float* __restrict__ rgb, float* __restrict__ fg_w,
+    float* __restrict__ bg_w, float* __restrict__ fg_rgb, float* __restrict__ fg_depth, float* __restrict__ bg_rgb,
+    float* __restrict__ bg_depth, float* __restrict__ bg_lambda) {
+    const int lane = lane_id();
+    int ray = blockIdx.x * kRaysPerBlock + wave_id();
+    const bool live = ray < a.n;
+    if (!live) ray = a.n - 1;
+    const V3 d = ld3(a.rd, ray);
+    const float norm = sqrtf(dot(d, d));
+    double f3[3], fd, b3[3] = {0.0, 0.0, 0.0}, bd = 0.0;
+    float lambda;
+    sweep<true>(a, ray, lane, norm, nullptr, nullptr, fg_w, live, f3, &fd, &lambda);
+    const int slot = slot_of[ray];
+    const bool has_bg = slot >= 0 && slot < n_live;          // (wave-uniform; a slot outside the live rows is never followed)
+    if (has_bg) {
+        // the unchanged sweep indexes raw_bg by the ray: hand it the array moved by (slot - ray) rows, so that row `ray` of
+        // what it sees is row `slot` of the live rows (an integer move: the moved base itself may lie outside the array)
+        CompArgs b = a;
+        b.raw_bg = reinterpret_cast<const float*>(reinterpret_cast<uintptr_t>(a.raw_bg)
+                                                  + (uintptr_t)(((long)slot - ray) * a.sb * 4 * (long)sizeof(float)));
+        sweep<false>(b, ray, lane, norm, nullptr, nullptr, bg_w, live, b3, &bd, nullptr);
+    } else if (live && bg_w) {
+        for (int i = lane; i < a.sb; i += kWave) bg_w[(size_t)ray * a.sb + i] = 0.f;
+    }
+    if (live && lane == 0) {
+        for (int c = 0; c < 3; ++c) {
+            const float f = (float)f3[c], b = has_bg ? lambda * (float)b3[c] : 0.f;
+            fg_rgb[(size_t)ray * 3 + c] = f;
+            bg_rgb[(size_t)ray * 3 + c] = b;
+            rgb[(size_t)ray * 3 + c] = f + b;
+        }
+        fg_depth[ray] = (float)fd;
+        bg_depth[ray] = has_bg ? lambda * (float)bd : 0.f;
+        bg_lambda[ray] = lambda;
+    }
+}
+
 struct CompGrads {
     const float* g_rgb; const float* g_fg_w; const float* g_bg_w; const float* g_fg_rgb; const float* g_fg_depth;
     const float* g_bg_rgb; const float* g_bg_depth; const float* g_lambda;      // any may be NULL
@@ -685,6 +744,36 @@ extern "C" int scnerf_npp_composite_fwd(const float* raw_fg, const float* raw_bg
     hipLaunchKernelGGL(npp_composite_fwd_kernel, dim3(scn_ceil_div(n, kRaysPerBlock)), dim3(256), 0,
                        (hipStream_t)stream, a, rgb, fg_weights, bg_weights, fg_rgb, fg_depth, bg_rgb, bg_depth,
                        bg_lambda);
+    return scn_launch_status();
+}
+
+extern "C" int scnerf_npp_fg_lambda(const float* raw_fg, const float* fg_z, const float* fg_z_max, const float* ray_d,
+                                    float* bg_lambda, int n, int sf, void* stream) {
+    SCN_RETURN_IF(!raw_fg || !fg_z || !fg_z_max || !ray_d || !bg_lambda || n < 0 || sf < 1, SCN_EINVAL);
+    if (n == 0) return 0;
+    CompArgs a;
+    a.raw_fg = raw_fg; a.raw_bg = nullptr; a.fg_z = fg_z; a.fg_z_max = fg_z_max; a.bg_z = nullptr; a.rd = ray_d;
+    a.n = n; a.sf = sf; a.sb = 0;
+    hipLaunchKernelGGL(npp_fg_lambda_kernel, dim3(scn_ceil_div(n, kRaysPerBlock)), dim3(256), 0, (hipStream_t)stream, a,
+                       bg_lambda);
+    return scn_launch_status();
+}
+
+extern "C" int scnerf_npp_composite_fwd_skip(const float* raw_fg, const float* raw_bg_live, const float* fg_z,
+                                             const float* fg_z_max, const float* bg_z, const float* ray_d,
+                                             const int* slot_of, float* rgb, float* fg_weights, float* bg_weights,
+                                             float* fg_rgb, float* fg_depth, float* bg_rgb, float* bg_depth,
+                                             float* bg_lambda, int n, int n_live, int sf, int sb, void* stream) {
+    SCN_RETURN_IF(!raw_fg || !fg_z || !fg_z_max || !bg_z || !ray_d || !slot_of || !rgb || !fg_rgb || !fg_depth, SCN_EINVAL);
+    SCN_RETURN_IF(!bg_rgb || !bg_depth || !bg_lambda || n < 0 || sf < 1 || sb < 1, SCN_EINVAL);
+    SCN_RETURN_IF(n_live < 0 || n_live > n || (n_live > 0 && !raw_bg_live), SCN_EINVAL);
+    if (n == 0) return 0;
+    CompArgs a;
+    a.raw_fg = raw_fg; a.raw_bg = raw_bg_live; a.fg_z = fg_z; a.fg_z_max = fg_z_max; a.bg_z = bg_z; a.rd = ray_d;
+    a.n = n; a.sf = sf; a.sb = sb;
+    hipLaunchKernelGGL(npp_composite_fwd_skip_kernel, dim3(scn_ceil_div(n, kRaysPerBlock)), dim3(256), 0,
+                       (hipStream_t)stream, a, slot_of, n_live, rgb, fg_weights, bg_weights, fg_rgb, fg_depth, bg_rgb,
+                       bg_depth, bg_lambda);
     return scn_launch_status();
 }
 

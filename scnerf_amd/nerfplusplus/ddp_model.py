@@ -57,6 +57,12 @@ class _NerfNetFunction(torch.autograd.Function):
         lib = _capi.load()
         # (`track`: torch.is_grad_enabled() at the call; needs_input_grad alone stays True under torch.no_grad())
         train = track and any(ctx.needs_input_grad)
+        tails = {"rgb": (3,), "fg_weights": (sf,), "bg_weights": (sb,), "fg_rgb": (3,), "bg_rgb": (3,)}
+        if not train and n > 0 and ops.inference_skip_background() is not None:
+            # forward-only with ops.inference_skip_background(eps): the background of the rays whose foreground is not opaque
+            t = _NerfNetFunction._forward_skip_background(ops.inference_skip_background(), o, d, zmax, zf, zb, fg_net, bg_net)
+            ctx.train = False
+            return tuple(t[k].view(*dots, *tails.get(k, ())) for k in _OUT_KEYS)
         fg_pts = torch.empty((n * sf, 3), dtype=torch.float32, device=dev)
         bg_pts = torch.empty((n * sb, 4), dtype=torch.float32, device=dev)
         views = torch.empty((n, 3), dtype=torch.float32, device=dev)
@@ -101,8 +107,46 @@ class _NerfNetFunction(torch.autograd.Function):
             ctx.state = (o, d, zmax, zf, zb, fg_pts, bg_pts, views, raw_f, raw_b, save_f, save_b,
                          ops.pack_weights(flat_f, "bwd", pd=3, remap=fg_net.pack_remap()),
                          ops.pack_weights(flat_b, "bwd", pd=4, remap=bg_net.pack_remap()), pl_f, pl_b, mx_f, mx_b)
-        tails = {"rgb": (3,), "fg_weights": (sf,), "bg_weights": (sb,), "fg_rgb": (3,), "bg_rgb": (3,)}
         return tuple(t[k].view(*dots, *tails.get(k, ())) for k in _OUT_KEYS)
+
+    @staticmethod
+    def _forward_skip_background(eps, o, d, zmax, zf, zb, fg_net, bg_net):
+        """The forward-only call under ops.inference_skip_background(eps) -> the eight outputs [n, ...] by name.  The
+        foreground points and network as ever; npp_fg_lambda -- the compositing's own foreground sweep -- gives bg_lambda;
+        compaction of the rays with bg_lambda > eps (one host read: the count sizes the launches).  All rays live: the
+        background points, the background network and scnerf_npp_composite_fwd on every ray, the switch-off launches.
+        None live: neither background launch.  Otherwise both on the live rows of ray_o, ray_d and bg_z, and
+        scnerf_npp_composite_fwd_skip reads the background through slot_of.  The guard records stay the dense passes'."""
+        n, sf, sb, dev = o.shape[0], zf.shape[1], zb.shape[1], o.device
+        lib = _capi.load()
+        fg_pts = torch.empty((n * sf, 3), dtype=torch.float32, device=dev)
+        views = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        _capi.check(lib.scnerf_npp_points_fwd(_p(o), _p(d), _p(zf), None, _p(fg_pts), None, _p(views), None, n, sf, 0,
+                                              _stream()), "scnerf_npp_points_fwd")
+        wf_f, pl_f = ops.network_packs(fg_net, fg_net.flat_parameters(), False, n, 3, remap=fg_net.pack_remap())
+        guards = ops.guard_records(dev, [("nerfpp_fg", n * sf), ("nerfpp_bg", n * sb)], fast=pl_f.fast) \
+            if isinstance(pl_f, ops.ResidentWeights) else {}
+        raw_f = ops.mlp_fwd(fg_pts, views, sf, wf_f, None, pd=3, planes=pl_f, guard=guards.get("nerfpp_fg"))
+        live_idx, slot_of, n_live = ops.background_compact(ops.npp_fg_lambda(raw_f, zf, zmax, d), eps)
+        if n_live == 0:
+            return ops.npp_composite_fwd_skip(raw_f, None, zf, zmax, zb, d, slot_of, 0)
+        dense = n_live == n
+        o_l, d_l, zb_l = (o, d, zb) if dense else (ops.ray_rows_gather(x, live_idx, n_live) for x in (o, d, zb))
+        bg_pts = torch.empty((n_live * sb, 4), dtype=torch.float32, device=dev)
+        views_l = views if dense else torch.empty((n_live, 3), dtype=torch.float32, device=dev)
+        _capi.check(lib.scnerf_npp_points_fwd(_p(o_l), _p(d_l), None, _p(zb_l), None, _p(bg_pts), None if dense else _p(views_l),
+                                              None, n_live, 0, sb, _stream()), "scnerf_npp_points_fwd")
+        wf_b, pl_b = ops.network_packs(bg_net, bg_net.flat_parameters(), False, n_live, 4, remap=bg_net.pack_remap())
+        raw_b = ops.mlp_fwd(bg_pts, views_l, sb, wf_b, None, pd=4, planes=pl_b, guard=guards.get("nerfpp_bg"))
+        if not dense:
+            return ops.npp_composite_fwd_skip(raw_f, raw_b, zf, zmax, zb, d, slot_of, n_live)
+        out = {"rgb": (n, 3), "fg_weights": (n, sf), "bg_weights": (n, sb), "fg_rgb": (n, 3), "fg_depth": (n,),
+               "bg_rgb": (n, 3), "bg_depth": (n,), "bg_lambda": (n,)}
+        t = {k: torch.empty(sh, dtype=torch.float32, device=dev) for k, sh in out.items()}
+        _capi.check(lib.scnerf_npp_composite_fwd(_p(raw_f), _p(raw_b), _p(zf), _p(zmax), _p(zb), _p(d),
+                                                 *[_p(t[k]) for k in _OUT_KEYS], n, sf, sb, _stream()),
+                    "scnerf_npp_composite_fwd")
+        return t
 
     @staticmethod
     def backward(ctx, *g):

@@ -154,6 +154,9 @@ def render_single_image(rank, world_size, models, ray_sampler, chunk_size, camer
     one CPU gather per key, after a `.cpu()` per key and chunk)."""
     from collections import OrderedDict
     import torch.distributed as dist
+    device = torch.device("cuda", rank) if isinstance(rank, int) else torch.device(rank)
+    if not isinstance(rank, int):          # a device in place of a rank: the one process of world_size 1
+        rank = 0
     with torch.no_grad():
         if camera_idx is not None:
             ray_batch = ray_sampler.get_all(camera_model, camera_idx, None, rank)
@@ -164,7 +167,6 @@ def render_single_image(rank, world_size, models, ray_sampler, chunk_size, camer
         raise Exception('Number of pixels in the image is not divisible by the number of GPUs!\n\t# pixels: {}\n\t# GPUs: {}'
                         .format(n_pix, world_size))
     per = n_pix // world_size
-    device = torch.device("cuda", rank) if isinstance(rank, int) else torch.device(rank)
     mine = {k: v[rank * per:(rank + 1) * per].to(device) for k, v in ray_batch.items() if torch.is_tensor(v)}
     levels = models['cascade_level']
     packed = [torch.empty((per, 12), dtype=torch.float32, device=device) for _ in range(levels)]

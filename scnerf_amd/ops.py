@@ -379,7 +379,17 @@ def skip_empty_stats(reset: bool = False) -> dict:
 def ray_compact(acc: Tensor, tau: float):
     """acc [n] (the coarse stage's acc_map), tau -> (live_idx int32 [n], slot_of int32 [n], n_live): ray i is live unless
     acc[i] <= tau; live_idx[:n_live] are the live rays ascending, slot_of[i] a live ray's position among them, -1 for a
-    skipped one (csrc/ray_compact.hip).  WAITS for the launch: n_live is read from a pinned word behind an event."""
+    skipped one (csrc/ray_compact.hip).  WAITS for the launch: n_live is read from a pinned word behind an event.
+    Counted in skip_empty_stats()."""
+    live_idx, slot_of, n_live = _ray_compact(acc, tau)
+    _SKIP_EMPTY_STATS["rays"] += acc.numel()
+    _SKIP_EMPTY_STATS["skipped"] += acc.numel() - n_live
+    return live_idx, slot_of, n_live
+
+
+def _ray_compact(acc: Tensor, tau: float):
+    """ray_compact without a counter: the launch and the one host read, shared by inference_skip_empty (ray_compact) and
+    inference_skip_background (background_compact)"""
     _f(acc, "acc")
     n = acc.numel()
     both = torch.empty((2, n), dtype=torch.int32, device=acc.device)
@@ -393,8 +403,6 @@ def ray_compact(acc: Tensor, tau: float):
         ev.record()
         ev.synchronize()
     n_live = int(host[0])
-    _SKIP_EMPTY_STATS["rays"] += n
-    _SKIP_EMPTY_STATS["skipped"] += n - n_live
     return both[0], both[1], n_live
 
 
@@ -434,6 +442,107 @@ def ray_expand(slot_of: Tensor, n_live: int, live, coarse, s_tot: int, s_fine: i
                                         _p(z_vals), _p(z_samples), _stream())
     _capi.check(st, "scnerf_ray_expand")
     return rgb, disp, acc, depth, z_std, raw, z_vals, z_samples
+
+
+# ---- NeRF++: skipping the background behind an opaque foreground (csrc/nerfpp.hip, nerfplusplus/ddp_model.py) ----------------
+_INFERENCE_SKIP_BACKGROUND = _FloatSwitch("SCNERF_INFER_SKIP_BACKGROUND", 0.0, 1.0, "inference_skip_background")
+_SKIP_BACKGROUND_STATS = {"rays": 0, "skipped": 0}
+NPP_OUT_KEYS = ("rgb", "fg_weights", "bg_weights", "fg_rgb", "fg_depth", "bg_rgb", "bg_depth", "bg_lambda")
+
+
+def inference_skip_background(eps=None) -> Optional[float]:
+    """Forward-only NerfNet.forward calls (NeRF++) skip the background network of the rays whose foreground is opaque: a
+    float eps in [0, 1) switches it on, "off" (the default) off.  rgb = fg_rgb + bg_lambda * bg_rgb, and bg_lambda -- the
+    foreground's final transmittance -- is known after the foreground network alone: npp_fg_lambda computes it (the
+    compositing kernel's own foreground sweep, bit for bit its bg_lambda), a ray with bg_lambda <= eps is SKIPPED (a NaN
+    bg_lambda is not), the live rays' rows of ray_o, ray_d and bg_z are compacted in ray order, the background points and
+    the background network run on n_live * sb samples in the arithmetic and guard mode in force, and
+    npp_composite_fwd_skip composites with the background read through slot_of.  The call returns, bit for bit, what it
+    would return had the background network answered raw_bg = 0 on every sample of the skipped rays: there bg_weights is a
+    row of zeros, bg_rgb = 0, bg_depth = 0 and rgb == fg_rgb; every foreground output (fg_weights, fg_rgb, fg_depth,
+    bg_lambda) is unchanged on every ray.  A live ray's eight outputs are the switch-off call's: with resident_guard "off"
+    bit for bit those of the full-batch call (fp32, resident and one-product arithmetic: the forward is per-sample
+    independent), with a guard mode on those of a switch-off call on the live rays alone (the background guard record
+    stays sized for the dense pass).  All rays live continues on the switch-off route; none live launches neither the
+    background points nor the background network.
+    Error against switch off, per channel of a skipped ray: |d rgb_c| = bg_rgb_c(off) <= eps * (1 + 1e-6)^sb -- bg_rgb_c
+    = bg_lambda * sum_i w_i c_i with every colour a sigmoid <= 1 and the background weights summing to at most (1 + 1e-6)^sb
+    (weights so far plus the transmittance left grow by the factor 1 + 1e-6 per sample at most: DESIGN.md 4.7.5).
+    In a cascade (render_single_image) every level decides by its own bg_lambda; a ray skipped at the coarse level hands
+    zero bg_weights to the background sample_pdf, which then places uniform samples should the ray be live again at the
+    fine level.  The foreground chain is untouched: the fine foreground depths depend on fg_weights alone.
+    Honoured by a forward-only NerfNet.forward with at least one ray (render_single_image, anything under
+    torch.no_grad()); a call that tracks gradients runs exactly as without the switch.  Composes with
+    inference_arithmetic("fast").
+    THE ONE HOST WAIT of the feature: n_live sizes the background launches, so every call waits on an event behind the
+    compaction kernel and reads one 4-byte word from pinned memory (skip_background_stats() re-uses these reads;
+    skip_empty_stats() never sees them).
+    Without an argument: the threshold in force, None when off.  Environment preset: SCNERF_INFER_SKIP_BACKGROUND."""
+    return _INFERENCE_SKIP_BACKGROUND(eps)
+
+
+def skip_background_stats(reset: bool = False) -> dict:
+    """{"rays": rays compacted by inference_skip_background so far, "skipped": those of them whose background was
+    skipped}: host-side sums of the counts background_compact has already read (no device access); `reset` zeroes them
+    after the read."""
+    out = dict(_SKIP_BACKGROUND_STATS)
+    if reset:
+        _SKIP_BACKGROUND_STATS["rays"] = _SKIP_BACKGROUND_STATS["skipped"] = 0
+    return out
+
+
+def background_compact(bg_lambda: Tensor, eps: float):
+    """ray_compact's launch and host read on acc = bg_lambda, tau = eps (ray i is live unless bg_lambda[i] <= eps) ->
+    (live_idx, slot_of, n_live); counted in skip_background_stats(), not in skip_empty_stats()."""
+    live_idx, slot_of, n_live = _ray_compact(bg_lambda, eps)
+    _SKIP_BACKGROUND_STATS["rays"] += bg_lambda.numel()
+    _SKIP_BACKGROUND_STATS["skipped"] += bg_lambda.numel() - n_live
+    return live_idx, slot_of, n_live
+
+
+def npp_fg_lambda(raw_fg: Tensor, fg_z: Tensor, fg_z_max: Tensor, ray_d: Tensor) -> Tensor:
+    """raw_fg [n * sf, 4], fg_z [n, sf], fg_z_max [n], ray_d [n, 3] -> bg_lambda [n], the foreground's final transmittance:
+    npp_composite_fwd's value bit for bit, without the background (csrc/nerfpp.hip)"""
+    n, sf = fg_z.shape
+    for t_, size, name in ((raw_fg, n * sf * 4, "raw_fg"), (fg_z, n * sf, "fg_z"), (fg_z_max, n, "fg_z_max"), (ray_d, n * 3, "ray_d")):
+        if _f(t_, name).numel() != size:
+            raise ValueError("npp_fg_lambda: %s holds %d floats where %d belong" % (name, t_.numel(), size))
+    lam = torch.empty((n,), dtype=torch.float32, device=fg_z.device)
+    st = _capi.load().scnerf_npp_fg_lambda(_p(raw_fg), _p(fg_z), _p(fg_z_max), _p(ray_d), _p(lam), n, sf, _stream())
+    _capi.check(st, "scnerf_npp_fg_lambda")
+    return lam
+
+
+def npp_composite_fwd_skip(raw_fg: Tensor, raw_bg_live: Optional[Tensor], fg_z: Tensor, fg_z_max: Tensor, bg_z: Tensor,
+                           ray_d: Tensor, slot_of: Tensor, n_live: int) -> dict:
+    """NerfNet.forward's compositing with the background of the live rays only: raw_bg_live [n_live * sb, 4] (None when
+    n_live == 0), slot_of [n] int32 (background_compact's) -> the eight outputs (NPP_OUT_KEYS) for all n rays, every
+    element written by the one launch; a skipped ray's are those of a zero raw_bg row."""
+    n, sf = fg_z.shape
+    sb = bg_z.shape[-1]
+    n_live = int(n_live)
+    if not 0 <= n_live <= n:
+        raise ValueError("n_live outside [0, n]")
+    _chk(slot_of, torch.int32, "slot_of")
+    sizes = [(raw_fg, n * sf * 4, "raw_fg"), (fg_z, n * sf, "fg_z"), (fg_z_max, n, "fg_z_max"), (bg_z, n * sb, "bg_z"),
+             (ray_d, n * 3, "ray_d"), (slot_of, n, "slot_of")]
+    if n_live or raw_bg_live is not None:
+        if raw_bg_live is None:
+            raise ValueError("live rays without their background outputs")
+        sizes.append((raw_bg_live, n_live * sb * 4, "raw_bg_live"))
+    for t_, size, name in sizes:
+        if t_ is not slot_of:
+            _f(t_, name)
+        if t_.numel() != size:
+            raise ValueError("npp_composite_fwd_skip: %s holds %d elements where %d belong" % (name, t_.numel(), size))
+    shapes = {"rgb": (n, 3), "fg_weights": (n, sf), "bg_weights": (n, sb), "fg_rgb": (n, 3), "fg_depth": (n,),
+              "bg_rgb": (n, 3), "bg_depth": (n,), "bg_lambda": (n,)}
+    out = {k: torch.empty(shapes[k], dtype=torch.float32, device=fg_z.device) for k in NPP_OUT_KEYS}
+    st = _capi.load().scnerf_npp_composite_fwd_skip(_p(raw_fg), _p(raw_bg_live) if n_live else None, _p(fg_z), _p(fg_z_max),
+                                                    _p(bg_z), _p(ray_d), _p(slot_of), *[_p(out[k]) for k in NPP_OUT_KEYS], n,
+                                                    n_live, sf, sb, _stream())
+    _capi.check(st, "scnerf_npp_composite_fwd_skip")
+    return out
 
 
 # ---- skipping samples in empty space: the occupancy grid (csrc/occupancy.hip, scnerf_amd/occupancy.py) ----------------------
