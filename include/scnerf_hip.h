@@ -812,6 +812,28 @@ int scnerf_occ_accumulate(const float* raw, float sigma_min, long long first_cel
                           void* stream);
 int scnerf_occ_dilate(const int* bits_in, int* bits_out, int R, void* stream);
 
+/* The grid of the NeRF++ background network, in the inverted-sphere space (csrc/npp_occupancy.hip): a sample is a row
+ * (x', y', z', w), a unit direction and w = 1 / r in [0, 1]; q_a = p_a * p_w -- one fp32 multiplication, rounded once -- lies in
+ * the unit ball, and q takes the test above, t_a = (q_a - lo_a) * inv_a, on the same bit lattice over a box [lo, hi) in q.  A
+ * NaN component and a q outside the box are live; w = 0 gives q = +-0, inside when lo < 0 < hi.
+ * scnerf_occ_compact4: scnerf_occ_compact on pts [n_samples][4]: pts_live [n_samples][4] receives the live rows, 16 bytes
+ * each (pts and pts_live 16-byte aligned), vd_live [n_samples][3] the direction of ray i / samples_per_ray; workspace:
+ * scnerf_occ_compact4_workspace_ints(n_samples) int32.  Two launches, no atomics.  The raw rows expand with
+ * scnerf_occ_expand_raw.
+ * scnerf_occ_probe_points_inverted: scnerf_occ_probe_points' lattice point q of every probe (the same formula) -> pts
+ * [n_cells k^3][4] (16-byte aligned): r2 = ((qx qx) + (qy qy)) + (qz qz), r = sqrt(r2), the row (qx / r, qy / r, qz / r,
+ * min(r, 1)), every operation fp32 and correctly rounded; r == 0 gives (0, 0, 1, 0).  A lattice point outside the ball is
+ * probed on the sphere.  scnerf_occ_accumulate and scnerf_occ_dilate serve both spaces.
+ * SCN_EINVAL: as above, and samples_per_ray < 1, vd_stride < 3, a misaligned row array. */
+long long scnerf_occ_compact4_workspace_ints(long long n_samples);
+int scnerf_occ_compact4(const float* pts, long long n_samples, const float* viewdirs, int vd_stride, int samples_per_ray,
+                        const int* bits, int R, float lo_x, float lo_y, float lo_z, float inv_x, float inv_y, float inv_z,
+                        int* workspace, int* live_idx, int* slot_of, float* pts_live, float* vd_live, int* n_live_dev,
+                        int* n_live_host, void* stream);
+int scnerf_occ_probe_points_inverted(long long first_cell, long long n_cells, int R, int k, float lo_x, float lo_y, float lo_z,
+                                     float cell_x, float cell_y, float cell_z, float off0, float off1, float off2, float* pts,
+                                     void* stream);
+
 /* --------------------------------------------------------------- stopping rays once they are opaque: the depth segments --- */
 
 /* A stage of samples_per_ray = S samples per ray runs front to back in K segments; segment k holds the sample indices

@@ -140,6 +140,10 @@ PROTOTYPES = {
     "scnerf_occ_accumulate": [P, F, LL, LL, I, I, P, P],
     # bits_in, bits_out, R
     "scnerf_occ_dilate": [P, P, I, P],
+    # the inverted-sphere grid of the NeRF++ background (rows of four floats): scnerf_occ_compact's and
+    # scnerf_occ_probe_points' arguments
+    "scnerf_occ_compact4": [P, LL, P, I, I, P, I, F, F, F, F, F, F, P, P, P, P, P, P, P, P],
+    "scnerf_occ_probe_points_inverted": [LL, LL, I, I, F, F, F, F, F, F, F, F, F, P, P],
     # the depth segments of early ray termination: pts, n, samples_per_ray, first, len, alive, viewdirs, vd_stride, bits, R,
     # lo xyz, inv xyz, workspace, live_idx, slot_of, pts_live, vd_live, the two counts (device words, pinned host words)
     "scnerf_seg_compact": [P, LL, I, I, I, P, P, I, P, I, F, F, F, F, F, F, P, P, P, P, P, P, P, P],
@@ -159,6 +163,7 @@ SIZE_FUNCS = {"scnerf_mlp_save_floats": [I, LL], "scnerf_mlp_grad_floats": [LL],
               "scnerf_camera_bwd_workspace_floats": [I],
               "scnerf_live_compact_workspace_ints": [LL],
               "scnerf_occ_compact_workspace_ints": [LL],
+              "scnerf_occ_compact4_workspace_ints": [LL],
               "scnerf_seg_compact_workspace_ints": [LL],
               "scnerf_image_metrics_workspace_floats": [I, I, I, I, I]}
 

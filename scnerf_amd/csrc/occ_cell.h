@@ -53,6 +53,21 @@ __device__ __forceinline__ bool sample_live(const Grid& g, const float* __restri
     return ((g.bits[c >> 5] >> (unsigned)(c & 31)) & 1u) != 0u;
 }
 
+// The inverted-sphere space of the NeRF++ background network (csrc/npp_occupancy.hip): a sample is (x', y', z', w), a unit
+// direction and w = 1 / r in [0, 1]; q = (x' w, y' w, z' w) -- one fp32 multiplication per axis, rounded once -- maps the
+// outside of the unit sphere onto the unit ball, and q takes sample_live's test on the same R^3 bit lattice over a box in q.
+// A NaN component and a q outside the box are live; w = 0 gives q = +-0, inside when lo < 0 < hi.
+__device__ __forceinline__ bool sample_live_inverted(const Grid& g, float px, float py, float pz, float pw) {
+    const float fr = (float)g.R;
+    const float tx = mul_rn(sub_rn(mul_rn(px, pw), g.lo_x), g.inv_x);
+    const float ty = mul_rn(sub_rn(mul_rn(py, pw), g.lo_y), g.inv_y);
+    const float tz = mul_rn(sub_rn(mul_rn(pz, pw), g.lo_z), g.inv_z);
+    const bool inside = tx >= 0.f && tx < fr && ty >= 0.f && ty < fr && tz >= 0.f && tz < fr;      // (false with a NaN)
+    if (!inside) return true;
+    const long c = ((long)(int)tz * g.R + (int)ty) * g.R + (int)tx;
+    return ((g.bits[c >> 5] >> (unsigned)(c & 31)) & 1u) != 0u;
+}
+
 static inline bool bad_resolution(int R) { return R < 32 || R > 1024 || (R & 31) != 0; }
 
 }  // namespace occ

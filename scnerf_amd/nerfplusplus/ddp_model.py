@@ -58,9 +58,16 @@ class _NerfNetFunction(torch.autograd.Function):
         # (`track`: torch.is_grad_enabled() at the call; needs_input_grad alone stays True under torch.no_grad())
         train = track and any(ctx.needs_input_grad)
         tails = {"rgb": (3,), "fg_weights": (sf,), "bg_weights": (sb,), "fg_rgb": (3,), "bg_rgb": (3,)}
+        grids = _NerfNetFunction._grids(fg_net, bg_net, dev) if (not train and n > 0) else (None, None)
         if not train and n > 0 and ops.inference_skip_background() is not None:
             # forward-only with ops.inference_skip_background(eps): the background of the rays whose foreground is not opaque
-            t = _NerfNetFunction._forward_skip_background(ops.inference_skip_background(), o, d, zmax, zf, zb, fg_net, bg_net)
+            t = _NerfNetFunction._forward_skip_background(ops.inference_skip_background(), o, d, zmax, zf, zb, fg_net, bg_net,
+                                                          grids)
+            ctx.train = False
+            return tuple(t[k].view(*dots, *tails.get(k, ())) for k in _OUT_KEYS)
+        if grids != (None, None):
+            # forward-only with ops.inference_occupancy_nerfpp(fg, bg): each network on the samples its grid calls live
+            t = _NerfNetFunction._forward_occupancy(grids, o, d, zmax, zf, zb, fg_net, bg_net)
             ctx.train = False
             return tuple(t[k].view(*dots, *tails.get(k, ())) for k in _OUT_KEYS)
         fg_pts = torch.empty((n * sf, 3), dtype=torch.float32, device=dev)
@@ -110,13 +117,66 @@ class _NerfNetFunction(torch.autograd.Function):
         return tuple(t[k].view(*dots, *tails.get(k, ())) for k in _OUT_KEYS)
 
     @staticmethod
-    def _forward_skip_background(eps, o, d, zmax, zf, zb, fg_net, bg_net):
+    def _grids(fg_net, bg_net, dev):
+        """(fg grid, bg grid) of ops.inference_occupancy_nerfpp for a forward-only call, each checked against its network
+        (OccupancyStaleError) and against the rays' device (ValueError); (None, None) when the switch is off"""
+        grids = ops.inference_occupancy_nerfpp()
+        if grids is None:
+            return None, None
+        for grid, net in zip(grids, (fg_net, bg_net)):
+            if grid is None:
+                continue
+            grid.check(net)
+            if grid.bits.device != dev:
+                raise ValueError("the occupancy grid lives on %s, the rays on %s" % (grid.bits.device, dev))
+        return grids
+
+    @staticmethod
+    def _network(which, grid, pts, views, spr, wf, pl, guard):
+        """one network of a forward-only call -> raw [P, 4]: the dense pass, or -- with a grid -- the pass on the samples the
+        grid calls live, expanded with zero rows (ops.nerfpp_network_under_grid)"""
+        if grid is None:
+            return ops.mlp_fwd(pts, views, spr, wf, None, pd=3 if which == "fg" else 4, planes=pl, guard=guard)
+        return ops.nerfpp_network_under_grid(which, grid, pts, views, spr, wf, pl, guard)
+
+    @staticmethod
+    def _forward_occupancy(grids, o, d, zmax, zf, zb, fg_net, bg_net):
+        """The forward-only call under ops.inference_occupancy_nerfpp(fg, bg) -> the eight outputs [n, ...] by name.  The
+        points kernel as it is; per network with a grid: compaction of the samples the grid does not call dead (one host
+        read: the count sizes the launch), the network on that list with one view direction per sample, expansion with
+        zero rows; a network without a grid runs dense.  scnerf_npp_composite_fwd unchanged.  All samples live goes the same
+        way, none live launches no network.  The guard records stay the dense passes'."""
+        n, sf, sb, dev = o.shape[0], zf.shape[1], zb.shape[1], o.device
+        lib = _capi.load()
+        fg_pts = torch.empty((n * sf, 3), dtype=torch.float32, device=dev)
+        bg_pts = torch.empty((n * sb, 4), dtype=torch.float32, device=dev)
+        views = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        _capi.check(lib.scnerf_npp_points_fwd(_p(o), _p(d), _p(zf), _p(zb), _p(fg_pts), _p(bg_pts), _p(views), None,
+                                              n, sf, sb, _stream()), "scnerf_npp_points_fwd")
+        wf_f, pl_f = ops.network_packs(fg_net, fg_net.flat_parameters(), False, n, 3, remap=fg_net.pack_remap())
+        wf_b, pl_b = ops.network_packs(bg_net, bg_net.flat_parameters(), False, n, 4, remap=bg_net.pack_remap())
+        guards = ops.guard_records(dev, [("nerfpp_fg", n * sf), ("nerfpp_bg", n * sb)], fast=pl_f.fast) \
+            if isinstance(pl_f, ops.ResidentWeights) else {}
+        raw_f = _NerfNetFunction._network("fg", grids[0], fg_pts, views, sf, wf_f, pl_f, guards.get("nerfpp_fg"))
+        raw_b = _NerfNetFunction._network("bg", grids[1], bg_pts, views, sb, wf_b, pl_b, guards.get("nerfpp_bg"))
+        out = {"rgb": (n, 3), "fg_weights": (n, sf), "bg_weights": (n, sb), "fg_rgb": (n, 3), "fg_depth": (n,),
+               "bg_rgb": (n, 3), "bg_depth": (n,), "bg_lambda": (n,)}
+        t = {k: torch.empty(sh, dtype=torch.float32, device=dev) for k, sh in out.items()}
+        _capi.check(lib.scnerf_npp_composite_fwd(_p(raw_f), _p(raw_b), _p(zf), _p(zmax), _p(zb), _p(d),
+                                                 *[_p(t[k]) for k in _OUT_KEYS], n, sf, sb, _stream()),
+                    "scnerf_npp_composite_fwd")
+        return t
+
+    @staticmethod
+    def _forward_skip_background(eps, o, d, zmax, zf, zb, fg_net, bg_net, grids=(None, None)):
         """The forward-only call under ops.inference_skip_background(eps) -> the eight outputs [n, ...] by name.  The
         foreground points and network as ever; npp_fg_lambda -- the compositing's own foreground sweep -- gives bg_lambda;
         compaction of the rays with bg_lambda > eps (one host read: the count sizes the launches).  All rays live: the
         background points, the background network and scnerf_npp_composite_fwd on every ray, the switch-off launches.
         None live: neither background launch.  Otherwise both on the live rows of ray_o, ray_d and bg_z, and
-        scnerf_npp_composite_fwd_skip reads the background through slot_of.  The guard records stay the dense passes'."""
+        scnerf_npp_composite_fwd_skip reads the background through slot_of.  The guard records stay the dense passes'.
+        `grids` (ops.inference_occupancy_nerfpp): the foreground network under its grid -- bg_lambda comes from the
+        expanded raw --, the background network under its grid on the points of the live rays."""
         n, sf, sb, dev = o.shape[0], zf.shape[1], zb.shape[1], o.device
         lib = _capi.load()
         fg_pts = torch.empty((n * sf, 3), dtype=torch.float32, device=dev)
@@ -126,7 +186,7 @@ class _NerfNetFunction(torch.autograd.Function):
         wf_f, pl_f = ops.network_packs(fg_net, fg_net.flat_parameters(), False, n, 3, remap=fg_net.pack_remap())
         guards = ops.guard_records(dev, [("nerfpp_fg", n * sf), ("nerfpp_bg", n * sb)], fast=pl_f.fast) \
             if isinstance(pl_f, ops.ResidentWeights) else {}
-        raw_f = ops.mlp_fwd(fg_pts, views, sf, wf_f, None, pd=3, planes=pl_f, guard=guards.get("nerfpp_fg"))
+        raw_f = _NerfNetFunction._network("fg", grids[0], fg_pts, views, sf, wf_f, pl_f, guards.get("nerfpp_fg"))
         live_idx, slot_of, n_live = ops.background_compact(ops.npp_fg_lambda(raw_f, zf, zmax, d), eps)
         if n_live == 0:
             return ops.npp_composite_fwd_skip(raw_f, None, zf, zmax, zb, d, slot_of, 0)
@@ -137,7 +197,7 @@ class _NerfNetFunction(torch.autograd.Function):
         _capi.check(lib.scnerf_npp_points_fwd(_p(o_l), _p(d_l), None, _p(zb_l), None, _p(bg_pts), None if dense else _p(views_l),
                                               None, n_live, 0, sb, _stream()), "scnerf_npp_points_fwd")
         wf_b, pl_b = ops.network_packs(bg_net, bg_net.flat_parameters(), False, n_live, 4, remap=bg_net.pack_remap())
-        raw_b = ops.mlp_fwd(bg_pts, views_l, sb, wf_b, None, pd=4, planes=pl_b, guard=guards.get("nerfpp_bg"))
+        raw_b = _NerfNetFunction._network("bg", grids[1], bg_pts, views_l, sb, wf_b, pl_b, guards.get("nerfpp_bg"))
         if not dense:
             return ops.npp_composite_fwd_skip(raw_f, raw_b, zf, zmax, zb, d, slot_of, n_live)
         out = {"rgb": (n, 3), "fg_weights": (n, sf), "bg_weights": (n, sb), "fg_rgb": (n, 3), "fg_depth": (n,),

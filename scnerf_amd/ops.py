@@ -575,8 +575,79 @@ def inference_occupancy(grid=None):
             from .occupancy import OccupancyGrid
             if not isinstance(grid, OccupancyGrid):
                 raise ValueError("inference_occupancy is \"off\" or an OccupancyGrid, not %r" % (grid,))
+            if grid.space != "euclidean":
+                raise ValueError("inference_occupancy takes a euclidean grid; an inverted-sphere grid belongs to the "
+                                 "background slot of inference_occupancy_nerfpp")
             _INFERENCE_OCCUPANCY[0] = grid
     return _INFERENCE_OCCUPANCY[0]
+
+
+_INFERENCE_OCCUPANCY_NERFPP = [None]
+_OCCUPANCY_NERFPP_STATS = {"fg_samples": 0, "fg_skipped": 0, "bg_samples": 0, "bg_skipped": 0}
+
+
+def inference_occupancy_nerfpp(fg=None, bg=None):
+    """Forward-only NerfNet.forward calls (NeRF++: render_single_image, anything under torch.no_grad()) skip both networks
+    on the samples a baked grid calls empty: `fg`, a euclidean occupancy.OccupancyGrid over the foreground network (its
+    samples o + z d lie in the unit sphere: the natural box is [-1, 1]^3), and `bg`, an inverted-sphere grid over the
+    background network, switch it on -- either may be None --, "off" (the default) off.  occupancy.bake_nerfpp bakes both.
+    A foreground sample is dead by inference_occupancy's cell test.  A background sample (x', y', z', w = 1 / r) is DEAD only
+    when q = (x' w, y' w, z' w) -- one fp32 multiplication per axis, the bijection of the outside of the unit sphere onto the
+    unit ball -- lies inside the grid's box and the bit of its cell is 0; a q outside the box and a NaN component are live.
+    The call returns, bit for bit, what it would return had the network answered raw = (0, 0, 0, 0) for every dead sample;
+    the live samples keep their bits in the fp32, resident and one-product arithmetics, and each cascade level's sampler
+    sees the weights that result.  Per network with a grid: the points kernel as it is, the live samples compacted in sample
+    order (occ_compact / occ_compact4), mlp_fwd on that list with samples_per_ray = 1 in the arithmetic and guard mode in
+    force (the guard record stays the dense pass's), the result expanded with zero rows (occ_expand_raw), the unchanged
+    compositing.  All samples live goes the same way; none live launches no network.  Composes with
+    inference_skip_background(eps): the foreground under its grid, bg_lambda from the expanded raw, ray compaction, the
+    background points of the live rays, the background grid on them.  A call that tracks gradients never sees the switch.
+    A grid baked from networks checks them (OccupancyStaleError); a grid on another device than the rays, and a grid of the
+    wrong space in either slot, is a ValueError.  inference_occupancy's grid stays ignored by the NeRF++ node.
+    ONE HOST WAIT PER NETWORK WITH A GRID AND CALL: the count sizes the network launch (occupancy_nerfpp_stats() re-uses
+    these reads; occupancy_stats() never sees them).
+    Without arguments: (fg, bg) in force, None when off.  No environment preset: a grid is not a string."""
+    if fg is None and bg is None:
+        return _INFERENCE_OCCUPANCY_NERFPP[0]
+    if isinstance(fg, str) and fg == "off" and bg is None:
+        _INFERENCE_OCCUPANCY_NERFPP[0] = None
+        return None
+    from .occupancy import OccupancyGrid
+    for grid, space, slot in ((fg, "euclidean", "fg"), (bg, "inverted_sphere", "bg")):
+        if grid is None:
+            continue
+        if not isinstance(grid, OccupancyGrid):
+            raise ValueError("inference_occupancy_nerfpp: %s is an OccupancyGrid or None, not %r" % (slot, grid))
+        if grid.space != space:
+            raise ValueError("inference_occupancy_nerfpp: the %s grid lies in the %s space, not in the %s space"
+                             % (slot, space, grid.space))
+    _INFERENCE_OCCUPANCY_NERFPP[0] = (fg, bg)
+    return _INFERENCE_OCCUPANCY_NERFPP[0]
+
+
+def occupancy_nerfpp_stats(reset: bool = False) -> dict:
+    """{"fg_samples", "fg_skipped", "bg_samples", "bg_skipped"}: the samples inference_occupancy_nerfpp compacted so far per
+    network and those of them dead -- host-side sums of the counts already read (no device access); `reset` zeroes them
+    after the read."""
+    out = dict(_OCCUPANCY_NERFPP_STATS)
+    if reset:
+        for k in _OCCUPANCY_NERFPP_STATS:
+            _OCCUPANCY_NERFPP_STATS[k] = 0
+    return out
+
+
+def nerfpp_network_under_grid(which: str, grid, pts: Tensor, viewdirs: Tensor, samples_per_ray: int, wf: Tensor, planes,
+                              guard=None) -> Tensor:
+    """The network `which` ("fg": pts [P, 3], "bg": pts [P, 4]) of a forward-only NeRF++ call under its grid -> raw [P, 4]:
+    compaction (one host read), mlp_fwd on the live samples with one view direction each, expansion with zero rows.
+    Counted in occupancy_nerfpp_stats()."""
+    pd = 3 if which == "fg" else 4
+    _, slot_of, pts_l, vd_l, n_live = _occ_compact(pts, viewdirs, samples_per_ray, grid, pd)
+    P = pts.numel() // pd
+    _OCCUPANCY_NERFPP_STATS[which + "_samples"] += P
+    _OCCUPANCY_NERFPP_STATS[which + "_skipped"] += P - n_live
+    raw_l = mlp_fwd(pts_l, vd_l, 1, wf, None, pd=pd, planes=planes, guard=guard) if n_live > 0 else None
+    return occ_expand_raw(raw_l, slot_of, n_live)
 
 
 def occupancy_stats(reset: bool = False) -> dict:
@@ -600,32 +671,52 @@ def occ_compact(pts: Tensor, viewdirs: Tensor, samples_per_ray: int, grid):
     """pts [P, 3] (sample i belongs to ray i // samples_per_ray), viewdirs [n, 3], grid (bits int32 [R^3 / 32], R, lo, inv)
     -> (live_idx int32 [P], slot_of int32 [P], pts_live [n_live, 3], vd_live [n_live, 3], n_live): the samples the grid does
     not call dead, ascending; slot_of[i] a live sample's position among them, -1 for a dead one (csrc/occupancy.hip).
-    WAITS for the launch: n_live is read from a pinned word behind an event."""
+    WAITS for the launch: n_live is read from a pinned word behind an event.  Counted in occupancy_stats()."""
+    if getattr(grid, "space", "euclidean") != "euclidean":
+        raise ValueError("occ_compact takes a euclidean grid; an inverted-sphere grid belongs to occ_compact4")
+    out = _occ_compact(pts, viewdirs, samples_per_ray, grid, 3)
+    _OCCUPANCY_STATS["samples"] += pts.numel() // 3
+    _OCCUPANCY_STATS["skipped"] += pts.numel() // 3 - out[4]
+    return out
+
+
+def occ_compact4(pts: Tensor, viewdirs: Tensor, samples_per_ray: int, grid):
+    """occ_compact for the samples of a NeRF++ background network: pts [P, 4] = (x', y', z', w), grid an inverted-sphere
+    grid over a box in q = (x' w, y' w, z' w) -> (live_idx, slot_of, pts_live [n_live, 4], vd_live [n_live, 3], n_live)
+    (csrc/npp_occupancy.hip).  WAITS for the launch as occ_compact does; counted in no statistic."""
+    if getattr(grid, "space", "euclidean") != "inverted_sphere":
+        raise ValueError("occ_compact4 takes an inverted-sphere grid")
+    return _occ_compact(pts, viewdirs, samples_per_ray, grid, 4)
+
+
+def _occ_compact(pts: Tensor, viewdirs: Tensor, samples_per_ray: int, grid, pd: int):
+    """occ_compact (pd = 3) and occ_compact4 (pd = 4) without a counter: the launch and the one host read, shared by
+    inference_occupancy and inference_occupancy_nerfpp"""
     _f(pts, "pts")
     R = _occ_resolution(grid.bits, grid.resolution)
     if grid.bits.device != pts.device:
         raise ValueError("the occupancy grid lives on %s, the samples on %s" % (grid.bits.device, pts.device))
-    P = pts.numel() // 3
+    P = pts.numel() // pd
     dev = pts.device
     vptr, vstride = _vd(viewdirs) if P > 0 else (None, 3)
     lib = _capi.load()
+    name = "scnerf_occ_compact" if pd == 3 else "scnerf_occ_compact4"
     ints = torch.empty((2, P), dtype=torch.int32, device=dev)
-    rows = torch.empty((2, P, 3), dtype=torch.float32, device=dev)
-    ws = torch.empty(int(lib.scnerf_occ_compact_workspace_ints(P)) + 1, dtype=torch.int32, device=dev)
+    rows_p = torch.empty((P, pd), dtype=torch.float32, device=dev)
+    rows_v = torch.empty((P, 3), dtype=torch.float32, device=dev)
+    ws = torch.empty(int(getattr(lib, name + "_workspace_ints")(P)) + 1, dtype=torch.int32, device=dev)
     # (CPU tensors: the interpreter build of the kernels under test, which runs the launch to its end)
     host = torch.empty(1, dtype=torch.int32, device="cpu", pin_memory=pts.is_cuda)
-    st = lib.scnerf_occ_compact(_p(pts) if P else None, P, vptr, vstride, int(samples_per_ray), _p(grid.bits), R, *grid.lo,
-                                *grid.inv, _p(ws[1:]), _p(ints[0]) if P else None, _p(ints[1]) if P else None,
-                                _p(rows[0]) if P else None, _p(rows[1]) if P else None, _p(ws[:1]), _p(host), _stream())
-    _capi.check(st, "scnerf_occ_compact")
+    st = getattr(lib, name)(_p(pts) if P else None, P, vptr, vstride, int(samples_per_ray), _p(grid.bits), R, *grid.lo,
+                            *grid.inv, _p(ws[1:]), _p(ints[0]) if P else None, _p(ints[1]) if P else None,
+                            _p(rows_p) if P else None, _p(rows_v) if P else None, _p(ws[:1]), _p(host), _stream())
+    _capi.check(st, name)
     if pts.is_cuda:
         ev = torch.cuda.Event()
         ev.record()
         ev.synchronize()
     n_live = int(host[0])
-    _OCCUPANCY_STATS["samples"] += P
-    _OCCUPANCY_STATS["skipped"] += P - n_live
-    return ints[0], ints[1], rows[0, :n_live], rows[1, :n_live], n_live
+    return ints[0], ints[1], rows_p[:n_live], rows_v[:n_live], n_live
 
 
 def occ_expand_raw(raw_live: Optional[Tensor], slot_of: Tensor, n_live: int) -> Tensor:
@@ -653,6 +744,21 @@ def occ_probe_points(first_cell: int, n_cells: int, R: int, k: int, lo, cell, de
     pts = torch.empty((int(n_cells) * k ** 3, 3), dtype=torch.float32, device=device)
     st = _capi.load().scnerf_occ_probe_points(int(first_cell), int(n_cells), int(R), k, *lo, *cell, *offs, _p(pts), _stream())
     _capi.check(st, "scnerf_occ_probe_points")
+    return pts
+
+
+def occ_probe_points_inverted(first_cell: int, n_cells: int, R: int, k: int, lo, cell, device) -> Tensor:
+    """occ_probe_points for an inverted-sphere grid -> pts [n_cells k^3, 4]: the lattice point q of every probe becomes
+    (q / r, min(r, 1)) with r = sqrt(((qx qx) + (qy qy)) + (qz qz)), every operation fp32 and correctly rounded; r == 0
+    gives (0, 0, 1, 0) (csrc/npp_occupancy.hip)."""
+    k = int(k)
+    if k not in (1, 2, 3):
+        raise ValueError("probes is 1, 2 or 3")
+    offs = [float(np.float32(np.float32(j + 0.5) / np.float32(k))) if j < k else 0.0 for j in range(3)]
+    pts = torch.empty((int(n_cells) * k ** 3, 4), dtype=torch.float32, device=device)
+    st = _capi.load().scnerf_occ_probe_points_inverted(int(first_cell), int(n_cells), int(R), k, *lo, *cell, *offs, _p(pts),
+                                                       _stream())
+    _capi.check(st, "scnerf_occ_probe_points_inverted")
     return pts
 
 
