@@ -709,7 +709,8 @@ extern "C" int scnerf_camera_rays_bwd(const float* kps, const long long* cam_idx
         hipLaunchKernelGGL(camera_rays_bwd_kernel, dim3(scn_ceil_div(n, 256)), dim3(256), (size_t)lds_slots * 12 * sizeof(float),
                            st, a, g_o, g_d, workspace, d_grid_o, d_grid_d, (float*)nullptr, lds_slots);
     }
-    hipLaunchKernelGGL(camera_finish_kernel, dim3(scn_ceil_div(slots, 64)), dim3(64), 0, st, a, workspace,
+    // at least one block: thread 0 writes d_intr_noise, and an empty batch of per-ray poses has no slot at all
+    hipLaunchKernelGGL(camera_finish_kernel, dim3(scn_ceil_div(slots < 1 ? 1 : slots, 64)), dim3(64), 0, st, a, workspace,
                        d_intr_noise, d_extr_noise, d_extrinsic);
     return scn_launch_status();
 }
@@ -763,7 +764,7 @@ extern "C" int scnerf_npp_camera_rays_bwd(const long long* select, const float* 
         hipLaunchKernelGGL(camera_rays_bwd_kernel, dim3(scn_ceil_div(n, 256)), dim3(256), (size_t)lds_slots * 12 * sizeof(float),
                            st, a, g_o, g_d, workspace, d_grid_o, d_grid_d, dist2 ? d_dist2 : (float*)nullptr, lds_slots);
     }
-    hipLaunchKernelGGL(camera_finish_kernel, dim3(scn_ceil_div(slots, 64)), dim3(64), 0, st, a, workspace,
+    hipLaunchKernelGGL(camera_finish_kernel, dim3(scn_ceil_div(slots < 1 ? 1 : slots, 64)), dim3(64), 0, st, a, workspace,
                        d_intr_noise, d_extr_noise, d_extrinsic);
     return scn_launch_status();
 }

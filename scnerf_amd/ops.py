@@ -1962,6 +1962,8 @@ def camera_rays_fwd(cam: dict, n: int):
     dev = cam["intr_init"].device
     ro = torch.empty((n, 3), dtype=torch.float32, device=dev)
     rd = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    if n == 0:                          # an empty tensor has no address to hand over; there is nothing to launch
+        return ro, rd
     st = _capi.load().scnerf_camera_rays_fwd(*_cam_common(cam), _p(ro), _p(rd), n, _stream())
     _capi.check(st, "scnerf_camera_rays_fwd")
     return ro, rd
@@ -1977,7 +1979,9 @@ def camera_rays_bwd(cam: dict, n: int, g_o: Optional[Tensor], g_d: Optional[Tens
     d_ex = torch.empty((C, 9), dtype=torch.float32, device=dev) if ext is None else None
     d_go = torch.empty_like(cam["grid_o"]) if cam.get("grid_o") is not None else None
     d_gd = torch.empty_like(cam["grid_d"]) if cam.get("grid_d") is not None else None
-    d_E = torch.empty((n_ext, 4, 4), dtype=torch.float32, device=dev) if n_ext else None
+    d_E = torch.empty((n_ext, 4, 4), dtype=torch.float32, device=dev) if ext is not None else None
+    if n == 0:                          # the gradient of an empty batch: zeros, as the entry point would leave them
+        return tuple(None if t is None else t.zero_() for t in (d_in, d_ex, d_go, d_gd, d_E))
     ws = torch.empty(lib.scnerf_camera_bwd_workspace_floats(max(C, n_ext)), dtype=torch.float32, device=dev)
     st = lib.scnerf_camera_rays_bwd(*_cam_common(cam), _p(g_o), _p(g_d), _p(d_in), _p(d_ex), _p(d_go), _p(d_gd),
                                     _p(d_E), _p(ws), n, _stream())
@@ -1991,6 +1995,8 @@ def pinhole_rays(kps: Optional[Tensor], c2w: Tensor, focal: float, H: int, W: in
     n = H * W if kps is None else kps.shape[0]
     ro = torch.empty((n, 3), dtype=torch.float32, device=c2w.device)
     rd = torch.empty((n, 3), dtype=torch.float32, device=c2w.device)
+    if n == 0:
+        return ro, rd
     st = _capi.load().scnerf_pinhole_rays(_p(kps), 0 if kps is None else int(kps.shape[1]), _p(c2w),
                                           ctypes.c_float(float(focal)), H, W, _p(ro), _p(rd), n, _stream())
     _capi.check(st, "scnerf_pinhole_rays")
@@ -2000,6 +2006,8 @@ def pinhole_rays(kps: Optional[Tensor], c2w: Tensor, focal: float, H: int, W: in
 def ndc_fwd(H, W, f2: Tensor, near: float, o: Tensor, d: Tensor):
     import ctypes
     no, nd = torch.empty_like(o), torch.empty_like(d)
+    if o.shape[0] == 0:
+        return no, nd
     st = _capi.load().scnerf_ndc_fwd(H, W, _p(f2), ctypes.c_float(float(near)), _p(o), _p(d), _p(no), _p(nd),
                                      o.shape[0], _stream())
     _capi.check(st, "scnerf_ndc_fwd")
@@ -2010,6 +2018,8 @@ def ndc_bwd(H, W, f2, near, o, d, g_no, g_nd):
     import ctypes
     g_o, g_d = torch.empty_like(o), torch.empty_like(d)
     g_f = torch.empty(2, dtype=torch.float32, device=o.device)
+    if o.shape[0] == 0:
+        return g_o, g_d, g_f.zero_()
     st = _capi.load().scnerf_ndc_bwd(H, W, _p(f2), ctypes.c_float(float(near)), _p(o), _p(d), _p(g_no), _p(g_nd),
                                      _p(g_o), _p(g_d), _p(g_f), o.shape[0], _stream())
     _capi.check(st, "scnerf_ndc_bwd")
@@ -2109,6 +2119,8 @@ def pack_rays_fwd(H, W, f2: Optional[Tensor], ndc_near: float, o: Tensor, d: Ten
     _f(o, "rays_o"), _f(d, "rays_d")
     n = o.shape[0]
     out = torch.empty((n, cols), dtype=torch.float32, device=o.device)
+    if n == 0:
+        return out
     st = _capi.load().scnerf_pack_rays_fwd(int(H), int(W), _p(f2), ctypes.c_float(float(ndc_near)), _p(o), _p(d),
                                            ctypes.c_float(float(near)), ctypes.c_float(float(far)), int(cols), _p(out), n,
                                            _stream())
@@ -2121,6 +2133,8 @@ def pack_rays_bwd(H, W, f2: Optional[Tensor], ndc_near: float, o: Tensor, d: Ten
     _f(g, "g_ray_batch")
     g_o, g_d = torch.empty_like(o), torch.empty_like(d)
     g_f = torch.empty(2, dtype=torch.float32, device=o.device) if (want_f2 and f2 is not None) else None
+    if o.shape[0] == 0:
+        return g_o, g_d, None if g_f is None else g_f.zero_()
     st = _capi.load().scnerf_pack_rays_bwd(int(H), int(W), _p(f2), ctypes.c_float(float(ndc_near)), _p(o), _p(d), int(cols),
                                            _p(g), _p(g_o), _p(g_d), _p(g_f), o.shape[0], _stream())
     _capi.check(st, "scnerf_pack_rays_bwd")
